@@ -24,6 +24,8 @@ Contract (one JSON line on rank 0):
            (settled) STATE the GPU leg times, on rank 0 at N=1, in a subprocess with a wall-clock budget; next to it, in
            `sample`, the 1-thread restatement (oracle). Falls back to the restatement (kind "port", cores 1) where oracle/_ref is
            not built or the budget is exceeded. A reported baseline, not the target.
+  --dump-outputs DIR  after the timed steps, what the headline leg's last step computed (body state, contact manifolds) as
+           DIR/<name>.npy, so that two builds can be compared output for output (the scenes are seeded: same arguments, same inputs).
 """
 import argparse
 import json
@@ -201,10 +203,12 @@ def _free_port():
 
 def spawn_ranks(n):
     """`python bench.py --gpus N` without torchrun: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
-    and pass their output through. Fails loudly when the box has fewer GPUs (unless the functional-test switch is set)."""
-    ngpu = torch.cuda.device_count() if torch.cuda.is_available() else 0
-    if ngpu < n and os.environ.get("EDYN_BENCH_SHARE_GPU") != "1":
-        raise SystemExit(f"bench.py: --gpus {n} but this box has {ngpu} GPU(s) (EDYN_BENCH_SHARE_GPU=1 shares devices, functional tests only)")
+    and pass their output through. Fails loudly when the box has fewer GPUs (unless the functional-test switch is set; the launcher
+    then does not open the GPU itself, so that it adds no process to the ones sharing the device)."""
+    if os.environ.get("EDYN_BENCH_SHARE_GPU") != "1":
+        ngpu = torch.cuda.device_count() if torch.cuda.is_available() else 0
+        if ngpu < n:
+            raise SystemExit(f"bench.py: --gpus {n} but this box has {ngpu} GPU(s) (EDYN_BENCH_SHARE_GPU=1 shares devices, functional tests only)")
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
@@ -284,6 +288,42 @@ class Leg:
         self.w = None
         self.gath = None
         torch.cuda.empty_cache()
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6
+
+
+def dump_outputs(path, state, manifolds):
+    """--dump-outputs: what the timed leg computed in its last step, as a caller of the stepper receives it - the body state and the
+    contact manifolds (sorted by body pair; the slots past a manifold's point count zeroed) - one float32 / float64 .npy per array.
+    Outputs above DUMP_BYTES_MAX are cut to a fixed, seeded sample of rows (the same rows of every array of a group), whose indices
+    are written as <group>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    m = manifolds[np.lexsort((manifolds["body"][:, 1], manifolds["body"][:, 0]))]
+    pt = m["pt"]
+    live = np.arange(4)[None, :] < m["num_points"][:, None]
+    groups = {
+        "body": {"pos": state[0], "orn": state[1], "linvel": state[2], "angvel": state[3]},
+        "manifold": {"manifold_body": m["body"].astype(np.float64), "manifold_num_points": m["num_points"].astype(np.float64),
+                     "manifold_distance": np.where(live, pt["distance"], 0).astype(np.float32),
+                     "manifold_normal_impulse": np.where(live, pt["normal_impulse"], 0).astype(np.float32),
+                     "manifold_friction_impulse": np.where(live[..., None], pt["friction_impulse"], 0).astype(np.float32)},
+    }
+    total = sum(a.nbytes for g in groups.values() for a in g.values())
+    # sampled: every kept row also costs its float64 index; 64 kB are left for the .npy headers
+    with_index = total + 8 * (len(state[0]) + len(m))
+    keep = 1.0 if total <= DUMP_BYTES_MAX else (DUMP_BYTES_MAX - 65536) / with_index
+    for gname, arrays in groups.items():
+        n = len(next(iter(arrays.values())))
+        rows_path = os.path.join(path, f"{gname}_rows.npy")
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(n, int(n * keep), replace=False))
+            np.save(rows_path, rows.astype(np.float64))
+            arrays = {k: a[rows] for k, a in arrays.items()}
+        elif os.path.exists(rows_path):
+            os.unlink(rows_path)   # a sample index from an earlier, larger run would not belong to these arrays
+        for k, a in arrays.items():
+            np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
 
 
 def per_rank_proxy(workload, args, device_index, stream, ranks):
@@ -372,6 +412,9 @@ def main():
     ap.add_argument("--cpu-sample-steps", type=int, default=6)
     ap.add_argument("--cpu-warm-steps", type=int, default=3)
     ap.add_argument("--cpu-budget-s", type=float, default=240.0, help="wall-clock budget of the reference-engine CPU leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the headline leg's last-step outputs (body state, contact manifolds) as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB, a fixed seeded sample of rows beyond that)")
     ap.add_argument("--cpu-reference-leg", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-state", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -419,6 +462,8 @@ def main():
     tm = w.get_timings()
     state = w.get_state()
     finite = bool(np.isfinite(state[0]).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state, w.get_manifolds())
     read_gbs, copy_gbs = w.measure_bandwidth(1 << 30) if rank == 0 else (0.0, 0.0)
 
     out = None
