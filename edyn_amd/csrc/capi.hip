@@ -430,6 +430,17 @@ static void resolve_timings(edynhip_ctx *c) {
     t.steps = tm.recorded;
 }
 
+// The call's event count and list go to the pinned prefetch buffer on snap_stream, behind what c->stream has enqueued so far
+static int enqueue_event_prefetch(edynhip_ctx *c) {
+    EH_HIP(c, hipEventRecord(c->evp_np_done, c->stream));
+    EH_HIP(c, hipStreamWaitEvent(c->snap_stream, c->evp_np_done, 0));
+    EH_HIP(c, hipMemcpyAsync(c->evp_host, c->event_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->snap_stream));
+    EH_HIP(c, hipMemcpyAsync(c->evp_host + 64, c->events, (size_t)std::min(c->evp_max, c->event_cap) * sizeof(eh::ContactEvent), hipMemcpyDeviceToHost, c->snap_stream));
+    EH_HIP(c, hipEventRecord(c->evp_ready, c->snap_stream));
+    c->evp_state = 1;
+    return EDYNHIP_OK;
+}
+
 static int run_stages(edynhip_ctx *c, uint32_t mask) {
     c->timer.e = nullptr;
     c->full_step = mask == EDYNHIP_STAGE_ALL && c->clears_primed;
@@ -448,14 +459,7 @@ static int run_stages(edynhip_ctx *c, uint32_t mask) {
     rec(1);
     if (mask & EDYNHIP_STAGE_NARROWPHASE) EH_TRY(guarded(narrowphase(c)));
     rec(2);
-    if (c->evp_now && c->events) {   // every event of a step is emitted by the broadphase and the narrowphase: the list of this call is complete
-        EH_HIP(c, hipEventRecord(c->evp_np_done, c->stream));
-        EH_HIP(c, hipStreamWaitEvent(c->snap_stream, c->evp_np_done, 0));
-        EH_HIP(c, hipMemcpyAsync(c->evp_host, c->event_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->snap_stream));
-        EH_HIP(c, hipMemcpyAsync(c->evp_host + 64, c->events, (size_t)std::min(c->evp_max, c->event_cap) * sizeof(eh::ContactEvent), hipMemcpyDeviceToHost, c->snap_stream));
-        EH_HIP(c, hipEventRecord(c->evp_ready, c->snap_stream));
-        c->evp_state = 1;
-    }
+    if (c->evp_now && c->events) EH_TRY(enqueue_event_prefetch(c));   // every event of a step is emitted by the broadphase and the narrowphase: the list of this call is complete
     if (mask & EDYNHIP_STAGE_ISLANDS) EH_TRY(guarded(islands(c)));
     if (mask & EDYNHIP_STAGE_SOLVE) EH_TRY(guarded(solve(c)));   // records events 3..9
     rec(10);
@@ -1089,6 +1093,7 @@ static int step_stamped(edynhip_ctx *c, uint32_t nsteps, bool timed, double firs
     c->timer.recorded = 0;
     if (c->events) EH_HIP(c, hipMemsetAsync(c->event_count, 0, sizeof(uint32_t), c->stream));   // the events of THIS call
     c->evp_state = c->evp_max ? 2 : 0;
+    bool ran = false;
     for (uint32_t i = 0; i < nsteps; ++i) {
         c->evp_now = c->evp_max != 0 && i + 1 == nsteps;
         // island_manager::update runs put_islands_to_sleep() against the PREVIOUS step's stamp and only then takes the new one
@@ -1099,9 +1104,13 @@ static int step_stamped(edynhip_ctx *c, uint32_t nsteps, bool timed, double firs
         if (c->all_asleep) { ++c->step_index; c->sim_clock = stamp; continue; }
         const int rc = run_stages(c, EDYNHIP_STAGE_ALL);
         c->sim_clock = stamp;
+        ran = true;
         if (rc != EDYNHIP_OK) { c->evp_now = false; return rc; }
     }
     c->evp_now = false;
+    // a step before the last put every island to sleep and the last was skipped: the events of the steps that ran are
+    // still to be handed over (state 2 stays "no step ran, nothing happened")
+    if (c->evp_max != 0 && c->evp_state == 2 && ran) EH_TRY(enqueue_event_prefetch(c));
     return EDYNHIP_OK;
 }
 int edynhip_step(edynhip_ctx *c, uint32_t nsteps) {

@@ -942,7 +942,7 @@ inline void import_records(entt::registry &registry, gpu_stepper &s, const edynh
             const entt::entity e = s.bodies[i];
             const edynhip_body_record &r = recs[i];
             if (e == entt::null || !(r.flags & EDYNHIP_RECORD_DYNAMIC) || (r.flags & EDYNHIP_RECORD_REMOVED)) continue;   // static / kinematic: the registry is the authority
-            if (!sp.contains(e) || !sv.contains(e)) continue;   // stripped by the user since the last update (noticed by sync_removed next time)
+            if (!sp.contains(e) || !sq.contains(e) || !sv.contains(e) || !sw.contains(e)) continue;   // stripped by the user since the last update (noticed by sync_removed next time)
             auto &p = sp.get(e); p.x = r.pos[0]; p.y = r.pos[1]; p.z = r.pos[2];
             auto &q = sq.get(e); q.x = r.orn[0]; q.y = r.orn[1]; q.z = r.orn[2]; q.w = r.orn[3];
             auto &v = sv.get(e); v.x = r.linvel[0]; v.y = r.linvel[1]; v.z = r.linvel[2];
@@ -1079,12 +1079,14 @@ inline void apply_contact_events(entt::registry &registry, gpu_stepper &s, std::
     auto &pool_geometry = registry.storage<contact_point_geometry>(); auto &pool_impulse = registry.storage<contact_point_impulse>();
     auto &pool_point = registry.storage<contact_point>();
     auto make_manifold = [&](uint32_t a, uint32_t b) {
+        if (auto it = s.manifold_entities.find(manifold_key(a, b)); it != s.manifold_entities.end()) return it->second;   // already mirrored: one entity per pair
         const entt::entity e = registry.create();
         pool_manifold.emplace(e, contact_manifold{{body_of(a), body_of(b)}, 0u});
         s.manifold_entities[manifold_key(a, b)] = e;
         return e;
     };
     auto make_point = [&](uint32_t a, uint32_t b, uint64_t id) {
+        if (s.point_entities.find(id) != s.point_entities.end()) return;   // already mirrored: neither a second entity nor a second count
         auto mit = s.manifold_entities.find(manifold_key(a, b));
         const entt::entity parent = mit != s.manifold_entities.end() ? mit->second : make_manifold(a, b);
         const entt::entity e = registry.create();
@@ -1217,7 +1219,10 @@ inline void run_steps(entt::registry &registry, gpu_stepper &s, unsigned steps, 
         // current state + the edits), a scene change (the context may be re-created), no step to overlap with
         if (s.state_dirty) {
             { phase_timer t(s.tm.write_back); merge_user_edits(registry, s); }
-            { phase_timer t(s.tm.contacts); sync_contacts(registry, s); }
+            // the device's events are those of the pending snapshot's steps: skipped when a rebuild from the manifolds already covered them
+            edynhip_record_view view{};
+            if (s.cfg.materialize_contacts) check(s, edynhip_snapshot_map(s.ctx, &view));
+            if (!s.cfg.materialize_contacts || view.step_index > s.events_stale_through) { phase_timer t(s.tm.contacts); sync_contacts(registry, s); }
         } else {
             edynhip_record_view view{};
             { phase_timer t(s.tm.state_wait); check(s, edynhip_snapshot_map(s.ctx, &view)); }
@@ -1341,7 +1346,10 @@ inline void snap_presentation(entt::registry &registry, gpu_stepper &s) {
 }  // namespace detail
 
 // ---- edyn.hpp:66-150
+inline void detach(entt::registry &registry);
 inline void attach(entt::registry &registry, const init_config &config = {}) {
+    // attached before: that stepper goes first (its hooks hold a reference to it), as a detach + attach would
+    if (registry.ctx().find<detail::gpu_stepper>()) detach(registry);
     auto &s = registry.ctx().emplace<detail::gpu_stepper>();
     s.cfg = config;
     // destroyed bodies / constraints are noticed through on_destroy hooks, like the reference's island manager (island_manager.cpp:24-27)

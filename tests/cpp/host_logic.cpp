@@ -167,6 +167,37 @@ int main() {
     REQUIRE(ok);
     edyn::detach(registry);
     registry.destroy(bodies[40]);   // the hooks are gone with the stepper: nothing dangles
+
+    // ---- attach twice without detach: the first stepper goes with its hooks, the live one hears of every removal
+    {
+        entt::registry reg2;
+        edyn::attach(reg2, edyn::init_config{});
+        auto bd = edyn::rigidbody_def{};
+        bd.shape = edyn::box_shape{{0.5f, 0.5f, 0.5f}};
+        edyn::make_rigidbody(reg2, bd);
+        edyn::attach(reg2, edyn::init_config{});
+        auto &live = reg2.ctx().get<edyn::detail::gpu_stepper>();
+        REQUIRE(live.hooks_connected && live.bodies.empty());
+        bd.position = {3, 0, 0};
+        const auto a = edyn::make_rigidbody(reg2, bd);
+        bd.position = {6, 0, 0};
+        const auto b = edyn::make_rigidbody(reg2, bd);
+        REQUIRE(live.bodies.size() == 2);
+        live.removal_pending = false;
+        reg2.destroy(a);
+        REQUIRE(live.removal_pending);
+        // a write-back for a body the user stripped of orientation and angvel: the body is left alone, nothing is dereferenced
+        reg2.remove<edyn::orientation>(b);
+        reg2.remove<edyn::angvel>(b);
+        edynhip_body_record recs[2] = {};
+        recs[1].flags = EDYNHIP_RECORD_DYNAMIC;
+        recs[1].pos[0] = 42; recs[1].orn[3] = 1; recs[1].linvel[0] = 5;
+        edynhip_record_view view{};
+        view.records = recs; view.num_bodies = 2;
+        edyn::detail::import_records(reg2, live, view, true);
+        REQUIRE(reg2.get<edyn::position>(b).x == 6 && reg2.get<edyn::linvel>(b).x == 0);
+        edyn::detach(reg2);
+    }
     std::printf("HOST_LOGIC_OK\n");
     return 0;
 }

@@ -74,6 +74,22 @@ def test_shim_contact_entities_and_asynchronous_mode():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("prog", ["contact_mirror", "contact_mirror_entt"])
+def test_shim_contact_entities_mirror_the_device(prog):
+    """tests/cpp/contact_mirror.cpp: after every update the registry's contact_manifold / contact_point entities are, as sets, the
+    device's manifolds and points - 30 Hz frames over a pile that sleeps and is woken, step callbacks, clamped long frames, and the
+    asynchronous mode held to a synchronous twin through a landing whose events overflow the snapshot's slot, followed by
+    edyn::refresh. The landing's event count comes from the CPU oracle."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import contact_scenes as cs
+    assert cs.most_events_in_one_step(cs.landing_grid(), 40, vel_iters=10) > 4096   # more than the snapshot's event slot holds
+    subprocess.check_call(["make", "-s", "-C", CPP, prog])
+    out = subprocess.run([os.path.join(CPP, prog)], capture_output=True, text=True, timeout=300)
+    assert "CONTACT_MIRROR_OK" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.gpu
 def test_shim_polyhedra():
     """convex_mesh / polyhedron_shape / make_box_mesh through the shim - tests/cpp/polyhedra.cpp: meshes shared between bodies, created
     once per context and again when the context is re-created; polyhedral cubes rest like boxes. The final transforms agree with
