@@ -82,6 +82,12 @@ EVENT_MANIFOLD_CREATED, EVENT_MANIFOLD_DESTROYED, EVENT_POINT_CREATED, EVENT_POI
 RECORD_DTYPE = np.dtype([("pos", np.float32, 3), ("orn", np.float32, 4), ("linvel", np.float32, 3), ("angvel", np.float32, 3),
                          ("present_pos", np.float32, 3), ("present_orn", np.float32, 4), ("origin", np.float32, 3), ("flags", np.uint32)])
 RECORD_DYNAMIC, RECORD_ASLEEP, RECORD_HAS_ORIGIN, RECORD_REMOVED = 1, 2, 4, 8
+# edynhip_raycast_hit (32 B): edyn::raycast's raycast_result per ray (body ~0 = nothing hit, fraction FLT_MAX on a miss)
+RAYCAST_HIT_DTYPE = np.dtype([("body", np.uint32), ("fraction", np.float32), ("normal", np.float32, 3), ("feature", np.int32),
+                              ("feature_index", np.uint32), ("reserved", np.uint32)])
+RAYCAST_NONE, RAYCAST_BOX_FACE, RAYCAST_CYLINDER_FACE, RAYCAST_CYLINDER_SIDE_EDGE = 0, 1, 2, 3   # EDYNHIP_RAYCAST_FEATURE_*
+RAYCAST_CAPSULE_HEMISPHERE, RAYCAST_CAPSULE_SIDE, RAYCAST_POLYHEDRON_FACE = 4, 5, 6
+RAYCAST_BRUTE_FORCE = 1   # EDYNHIP_RAYCAST_BRUTE_FORCE (test aid: every ray tests every body)
 
 
 class RecordView(C.Structure):
@@ -108,7 +114,8 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_world_step", "edynhip_world_get_state", "edynhip_world_get_partition", "edynhip_world_repartition",
            "edynhip_world_get_manifolds", "edynhip_world_get_stats", "edynhip_world_context", "edynhip_partition_islands",
            "edynhip_island_boxes_overlap", "edynhip_get_island_boxes",
-           "edynhip_world_set_pair_filter", "edynhip_world_default_should_collide", "edynhip_get_sleep_timers", "edynhip_set_sleep_timers"]
+           "edynhip_world_set_pair_filter", "edynhip_world_default_should_collide", "edynhip_get_sleep_timers", "edynhip_set_sleep_timers",
+           "edynhip_raycast", "edynhip_raycast_device"]
 
 _lib = None
 
@@ -135,6 +142,8 @@ def lib():
         L.edynhip_set_state.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.edynhip_pack_state_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.edynhip_get_derived.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+        L.edynhip_raycast.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_raycast_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_num_manifolds.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.edynhip_get_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_set_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]

@@ -684,6 +684,22 @@ __global__ void k_ev_destroyed(uint32_t pm, Manifolds prev, uint8_t *matched, Ev
     matched[p] = 0;   // armed for the step in which this array is `prev` again
 }
 
+// The raycast's query tree (raycast.hip): the same Morton keys, sort, Karras build and ropes over `list` (n bodies, boxes amin / amax),
+// on buffers the broadphase never touches. The caller sets parent[] to ~0 beforehand (a one-leaf tree has no k_bp_build thread).
+int build_query_tree(edynhip_ctx *c, const uint32_t *list, uint32_t n, const float4 *amin, const float4 *amax, Counters *cnt,
+                     uint64_t *keys, uint64_t *keys_sorted, uint32_t *parent, uint32_t *left, uint32_t *right, uint32_t *visit, uint32_t *rope) {
+    if (n == 0) return EDYNHIP_OK;
+    hipStream_t s = c->stream;
+    hipLaunchKernelGGL(k_step_reset, dim3(1), dim3(64), 0, s, cnt);   // (its own counters block: only the bounds are read)
+    hipLaunchKernelGGL(k_bp_bounds, dim3(std::min(blocks(n, 256), 32u)), dim3(256), 0, s, list, n, amin, amax, cnt);
+    hipLaunchKernelGGL(k_bp_morton, dim3(blocks(n, 256)), dim3(256), 0, s, list, n, amin, amax, cnt, keys);
+    EH_TRY(sort_u64(c, keys, keys_sorted, n, 32, 62));
+    if (n > 1) hipLaunchKernelGGL(k_bp_build, dim3(blocks(n - 1, 256)), dim3(256), 0, s, keys_sorted, (int)n, parent, left, right, visit);
+    hipLaunchKernelGGL(k_bp_ropes, dim3(blocks(2 * n - 1, 256)), dim3(256), 0, s, (int)n, parent, right, rope);
+    EH_HIP(c, hipGetLastError());
+    return EDYNHIP_OK;
+}
+
 int broadphase(edynhip_ctx *c) {
     hipStream_t s = c->stream;
     const uint32_t np = c->bvh.num_proc;

@@ -443,6 +443,7 @@ static int enqueue_event_prefetch(edynhip_ctx *c) {
 
 static int run_stages(edynhip_ctx *c, uint32_t mask) {
     c->timer.e = nullptr;
+    ++c->state_epoch;   // (raycast.hip: the query tree is stale)
     c->full_step = mask == EDYNHIP_STAGE_ALL && c->clears_primed;
     if (mask == EDYNHIP_STAGE_ALL) EH_TRY(begin_timed_step(c));
     else c->force_islands = true;   // partial runs (tests) never rely on a previous step's labels
@@ -580,6 +581,7 @@ void edynhip_destroy(edynhip_ctx *c) {
         fprintf(stderr, "[edynhip] island labels: %llu steps relabelled in full, %llu incrementally\n", (unsigned long long)c->cc_full_steps, (unsigned long long)c->cc_incremental_steps);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    eh::raycast_free(c);
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->idx_scratch) (void)hipFree(c->idx_scratch);
     for (void *p : c->mesh_allocs) (void)hipFree(p);
@@ -633,6 +635,7 @@ static int rebuild_broadphase_lists(edynhip_ctx *c) {
     c->all_asleep = false;
     c->bvh.age = 0;   // the tree topology is rebuilt on the next step
     c->bvh.lists_dirty = true;
+    ++c->state_epoch;
     c->bvh.num_np = (uint32_t)np_list.size();
     c->bvh.num_proc = (uint32_t)proc_list.size();
     np_list.insert(np_list.end(), proc_list.begin(), proc_list.end());
@@ -1227,6 +1230,7 @@ int edynhip_set_state(edynhip_ctx *c, const float *pos, const float *orn, const 
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the staging buffers are reused by the next call
     if (e != hipSuccess) return set_error(c, EDYNHIP_ERR_HIP, "edynhip_set_state", e);
     c->bvh.lists_dirty = true;   // moved behind the broadphase's back: the candidate lists are rebuilt at the next step
+    ++c->state_epoch;
     if (c->sleeping) return edynhip_wake_all(c);   // an edited body wakes its island (wake_up_entity); all of them here
     return EDYNHIP_OK;
 }
@@ -1310,6 +1314,7 @@ int edynhip_refresh_derived(edynhip_ctx *c) {
     if (!c) return EDYNHIP_ERR_INVALID;
     EH_HIP(c, hipSetDevice(c->device));
     c->bvh.lists_dirty = true;
+    ++c->state_epoch;
     return refresh_derived(c);
 }
 
@@ -1358,6 +1363,7 @@ int edynhip_set_center_of_mass(edynhip_ctx *c, uint32_t body, const float *com3)
     hipLaunchKernelGGL(k_move_com, dim3(1), dim3(1), 0, c->stream, c->b, body, make_float3(com3[0], com3[1], com3[2]));
     EH_HIP(c, hipGetLastError());
     c->bvh.lists_dirty = true;   // (the reference does not wake the body's island either)
+    ++c->state_epoch;
     return EDYNHIP_OK;
 }
 int edynhip_get_asleep(edynhip_ctx *c, uint8_t *asleep) {

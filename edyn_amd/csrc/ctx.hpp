@@ -211,6 +211,8 @@ __host__ __device__ inline size_t pslot_at(uint32_t slot, uint32_t piece) {   //
     return (size_t)(p >> 5) * 192u + (piece << 6) + (slot & 63u);
 }
 
+struct RayTree;   // raycast.hip
+
 struct LBVH {
     uint64_t *keys = nullptr, *keys_sorted = nullptr;   // morton<<32 | body
     uint32_t *parent = nullptr;     // [2n-1]: internal 0..n-2, leaves n-1..2n-2
@@ -450,6 +452,10 @@ struct edynhip_ctx {
     uint32_t *excl = nullptr;      // collision exclusion lists [max_bodies][16], ~0u-terminated; allocated by the first edynhip_exclude_collision
     std::vector<uint32_t> host_excl;   // host mirror of excl (edits are rare: scene construction)
     std::vector<int32_t> host_kind, host_shape;   // per body, for rebuilding the broadphase lists when bodies are appended
+    // raycast queries (raycast.hip): a query tree of their own, rebuilt at the first raycast after state_epoch moved on
+    uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
+    eh::RayTree *ray = nullptr;
+    bool world_shard = false;      // a shard of a multi-device world (multi.hip): no raycast
 };
 
 namespace eh {
@@ -476,6 +482,10 @@ int sort_u64(edynhip_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n, int 
 int set_error(edynhip_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
 int mesh_bind_bodies(edynhip_ctx *c, uint32_t first, uint32_t n, const int32_t *shape_type, const float *shape_param);   // mesh.hip
 int update_rotated(edynhip_ctx *c);
+// the raycast's query tree (raycast.hip) is an LBVH of its own, built by the broadphase's kernels on its own buffers (broadphase.hip)
+int build_query_tree(edynhip_ctx *c, const uint32_t *list, uint32_t n, const float4 *amin, const float4 *amax, Counters *cnt,
+                     uint64_t *keys, uint64_t *keys_sorted, uint32_t *parent, uint32_t *left, uint32_t *right, uint32_t *visit, uint32_t *rope);
+void raycast_free(edynhip_ctx *c);   // raycast.hip
 }  // namespace eh
 
 #define EH_HIP(c, call)                                                          \

@@ -449,6 +449,7 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
         int status = 0;
         s.ctx = edynhip_create(&cfg, &status);
         if (!s.ctx) { s.rc = status; s.err = edynhip_last_error(nullptr); return; }
+        s.ctx->world_shard = true;   // (raycast.hip: a shard holds part of a world; raycasts on worlds are not provided)
         s.cap = cfg.max_bodies; s.joint_cap = cfg.max_joints;
         trace.mark("edynhip_create");
         for (const HostScene::Mesh &m : sc.meshes) {

@@ -444,6 +444,27 @@ class World:
         self._check(self._L.edynhip_get_derived(self._h, _ptr(aabb), _ptr(iw), _ptr(isl)))
         return aabb, iw, isl
 
+    # ---- raycast queries: edyn::raycast (collision/raycast.hpp) for batches of rays, answered on the device
+    def raycast(self, p0, p1, ignore=(), brute_force=False):
+        """Rays p0[i] -> p1[i] (arrays of shape (n, 3), or one ray of shape (3,)); returns a RAYCAST_HIT_DTYPE array of n records
+        (body ~0 and fraction FLT_MAX where nothing is hit). ignore: body indices left out; brute_force: test every body (no tree)."""
+        a = np.ascontiguousarray(np.asarray(p0, np.float32).reshape(-1, 3))
+        b = np.ascontiguousarray(np.asarray(p1, np.float32).reshape(-1, 3))
+        if a.shape != b.shape:
+            raise ValueError("p0 and p1 must hold the same number of points")
+        ign = np.ascontiguousarray(np.asarray(ignore, np.uint32).reshape(-1))
+        out = np.zeros(len(a), _capi.RAYCAST_HIT_DTYPE)
+        flags = _capi.RAYCAST_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_raycast(self._h, len(a), _ptr(a), _ptr(b), len(ign), _ptr(ign) if len(ign) else None, flags, _ptr(out)))
+        return out
+
+    def raycast_device(self, n, p0_ptr, p1_ptr, out_ptr, ignore=(), brute_force=False):
+        """Device pointers: p0 / p1 hold n float4 (w unused), out receives n 32-byte records; enqueued on the context's stream."""
+        ign = np.ascontiguousarray(np.asarray(ignore, np.uint32).reshape(-1))
+        flags = _capi.RAYCAST_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_raycast_device(self._h, int(n), C.c_void_p(p0_ptr), C.c_void_p(p1_ptr), len(ign),
+                                                   _ptr(ign) if len(ign) else None, flags, C.c_void_p(out_ptr)))
+
     def get_manifolds(self):
         m = C.c_uint32(0)
         self._check(self._L.edynhip_num_manifolds(self._h, C.byref(m)))

@@ -34,6 +34,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -1451,6 +1452,99 @@ inline void step_simulation(entt::registry &registry, double time) {
 }
 /// edyn::step_simulation(registry) (edyn.hpp:142).
 inline void step_simulation(entt::registry &registry) { step_simulation(registry, get_time(registry)); }
+
+// ---- collision/raycast.hpp:21-151: edyn::raycast, answered on the device (edynhip_raycast; definition and the quirks kept: DESIGN §8
+// "Raycast queries"). The info types keep the reference's names, members and variant order; compound / mesh / paged-mesh info are
+// declared for source compatibility and never produced (those shapes are not bodies here).
+enum class cylinder_feature : uint8_t { face, side_edge, cap_edge };   // shapes/cylinder_shape.hpp:11-18
+enum class capsule_feature : uint8_t { hemisphere, side };             // shapes/capsule_shape.hpp:11-14
+struct box_raycast_info { size_t face_index; };
+struct cylinder_raycast_info { cylinder_feature feature; size_t face_index; };
+struct capsule_raycast_info { capsule_feature feature; size_t hemisphere_index; };
+struct polyhedron_raycast_info { size_t face_index; };
+struct mesh_raycast_info { size_t triangle_index; };
+struct paged_mesh_raycast_info { size_t submesh_index; size_t triangle_index; };
+struct compound_raycast_info {
+    size_t child_index;
+    std::variant<std::monostate, box_raycast_info, cylinder_raycast_info, capsule_raycast_info, polyhedron_raycast_info> child_info_var;
+};
+struct shape_raycast_result {
+    scalar fraction{std::numeric_limits<scalar>::max()};
+    vector3 normal;
+    std::variant<std::monostate, box_raycast_info, cylinder_raycast_info, capsule_raycast_info, polyhedron_raycast_info,
+                 compound_raycast_info, mesh_raycast_info, paged_mesh_raycast_info> info_var;
+};
+struct raycast_result : public shape_raycast_result {
+    entt::entity entity{entt::null};
+    raycast_result &operator=(const shape_raycast_result &result) { shape_raycast_result::operator=(result); return *this; }
+};
+namespace detail {
+inline raycast_result to_raycast_result(const gpu_stepper &s, const edynhip_raycast_hit &h) {
+    raycast_result r;
+    r.fraction = h.fraction;
+    r.normal = vector3{h.normal[0], h.normal[1], h.normal[2]};
+    const size_t idx = h.feature_index == 0xFFFFFFFFu ? SIZE_MAX : (size_t)h.feature_index;
+    switch (h.feature) {
+    case EDYNHIP_RAYCAST_FEATURE_BOX_FACE: r.info_var = box_raycast_info{idx}; break;
+    case EDYNHIP_RAYCAST_FEATURE_CYLINDER_FACE: r.info_var = cylinder_raycast_info{cylinder_feature::face, idx}; break;
+    case EDYNHIP_RAYCAST_FEATURE_CYLINDER_SIDE_EDGE: r.info_var = cylinder_raycast_info{cylinder_feature::side_edge, idx}; break;
+    case EDYNHIP_RAYCAST_FEATURE_CAPSULE_HEMISPHERE: r.info_var = capsule_raycast_info{capsule_feature::hemisphere, idx}; break;
+    case EDYNHIP_RAYCAST_FEATURE_CAPSULE_SIDE: r.info_var = capsule_raycast_info{capsule_feature::side, idx}; break;
+    case EDYNHIP_RAYCAST_FEATURE_POLYHEDRON_FACE: r.info_var = polyhedron_raycast_info{idx}; break;
+    default: break;
+    }
+    if (h.body < s.bodies.size()) r.entity = s.bodies[h.body];
+    return r;
+}
+// The rays see what the registry holds: pending edits go up through the upload path edyn::update takes (a later update would have
+// uploaded them the same way before its first step, so nothing a step computes changes). Rejected loudly where not supported.
+inline void raycast_prepare(entt::registry &registry, gpu_stepper &s) {
+    if (s.cfg.execution_mode == execution_mode::asynchronous)
+        throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::raycast: not in execution_mode::asynchronous (the reference asks for raycast_async there, which this stepper does not provide)");
+    if (s.multi()) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::raycast: a world over several devices (init_config::devices) has no raycast");
+    sync_removed(registry, s);
+    if (s.scene_dirty) upload_scene(registry, s);
+    if (s.state_dirty) upload_state(registry, s);
+}
+inline std::vector<uint32_t> raycast_ignore(entt::registry &registry, const std::vector<entt::entity> &ignore) {
+    std::vector<uint32_t> out;
+    for (entt::entity e : ignore)
+        if (registry.valid(e))
+            if (auto *bi = registry.try_get<body_index>(e)) out.push_back(bi->value);
+    return out;
+}
+}  // namespace detail
+/// edyn::raycast (collision/raycast.hpp:139-151, raycast.cpp:20-56): the first body the segment p0 -> p1 hits.
+inline raycast_result raycast(entt::registry &registry, vector3 p0, vector3 p1, const std::vector<entt::entity> &ignore_entities = {}) {
+    auto &s = registry.ctx().get<detail::gpu_stepper>();
+    detail::raycast_prepare(registry, s);
+    if (!s.ctx || s.bodies.empty()) return raycast_result{};
+    const std::vector<uint32_t> ign = detail::raycast_ignore(registry, ignore_entities);
+    const float a[3] = {p0.x, p0.y, p0.z}, b[3] = {p1.x, p1.y, p1.z};
+    edynhip_raycast_hit h{};
+    detail::check(s, edynhip_raycast(s.ctx, 1, a, b, (uint32_t)ign.size(), ign.empty() ? nullptr : ign.data(), 0, &h));
+    return detail::to_raycast_result(s, h);
+}
+/// Extension (not in the reference): a batch of rays p0[i] -> p1[i] in one launch and one synchronisation; element i equals
+/// raycast(registry, p0[i], p1[i], ignore_entities).
+inline std::vector<raycast_result> raycast(entt::registry &registry, const std::vector<vector3> &p0, const std::vector<vector3> &p1,
+                                           const std::vector<entt::entity> &ignore_entities = {}) {
+    if (p0.size() != p1.size()) throw stepper_error(EDYNHIP_ERR_INVALID, "edyn::raycast: p0 and p1 differ in length");
+    auto &s = registry.ctx().get<detail::gpu_stepper>();
+    detail::raycast_prepare(registry, s);
+    std::vector<raycast_result> out(p0.size());
+    if (!s.ctx || s.bodies.empty() || p0.empty()) return out;
+    const std::vector<uint32_t> ign = detail::raycast_ignore(registry, ignore_entities);
+    std::vector<float> a(3 * p0.size()), b(3 * p0.size());
+    for (size_t i = 0; i < p0.size(); ++i) {
+        a[3 * i] = p0[i].x; a[3 * i + 1] = p0[i].y; a[3 * i + 2] = p0[i].z;
+        b[3 * i] = p1[i].x; b[3 * i + 1] = p1[i].y; b[3 * i + 2] = p1[i].z;
+    }
+    std::vector<edynhip_raycast_hit> h(p0.size());
+    detail::check(s, edynhip_raycast(s.ctx, (uint32_t)p0.size(), a.data(), b.data(), (uint32_t)ign.size(), ign.empty() ? nullptr : ign.data(), 0, h.data()));
+    for (size_t i = 0; i < p0.size(); ++i) out[i] = detail::to_raycast_result(s, h[i]);
+    return out;
+}
 
 // ---- util/rigidbody.hpp:84-93, rigidbody.cpp:47-191
 inline void make_rigidbody(entt::entity entity, entt::registry &registry, const rigidbody_def &def) {

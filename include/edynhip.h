@@ -273,6 +273,41 @@ int edynhip_pack_state_device(edynhip_ctx *ctx, void *dst_device, uint32_t first
 /* Derived per-body state: aabb[n][6] (min,max), inertia_world_inv[n][9], island label[n]; any may be NULL. */
 int edynhip_get_derived(edynhip_ctx *ctx, float *aabb, float *inertia_world_inv, uint32_t *island);
 
+/* edyn::raycast (include/edyn/collision/raycast.hpp:139-151, src/edyn/collision/raycast.cpp:20-56) for a batch of rays p0 -> p1.
+ * Candidates: every body that has a shape, is not removed and is not in `ignore` - sleeping, static and kinematic bodies and planes
+ * included - whose current AABB grown by 0.1 (dynamic_tree.hpp:24) the segment crosses (intersect_segment_aabb, geom.cpp:1185-1223).
+ * Each candidate is tested with the reference's shape_raycast for its shape (raycast.cpp:58-380) in the frame of its origin (its
+ * position when it has no centre-of-mass offset); the hit is the smallest fraction, an exact tie goes to the lowest body index. The
+ * reference's quirks are kept: box and plane fractions are not clipped to [0, 1]. A zero-length ray inside a box or polyhedron is
+ * undefined in the reference: the record then carries the reference's fraction, a zero normal and feature_index ~0u.
+ * The rays see the context's current state (the last step, or edynhip_set_state / edynhip_add_bodies ... since); the query tree is
+ * the context's own, rebuilt at the first raycast after a change, and a raycast changes nothing a later step computes. */
+enum { EDYNHIP_RAYCAST_FEATURE_NONE = 0,              /* sphere, plane, miss */
+       EDYNHIP_RAYCAST_FEATURE_BOX_FACE = 1,          /* box_raycast_info::face_index */
+       EDYNHIP_RAYCAST_FEATURE_CYLINDER_FACE = 2,     /* cylinder_raycast_info{cylinder_feature::face, face_index} */
+       EDYNHIP_RAYCAST_FEATURE_CYLINDER_SIDE_EDGE = 3,/* cylinder_raycast_info{cylinder_feature::side_edge} */
+       EDYNHIP_RAYCAST_FEATURE_CAPSULE_HEMISPHERE = 4,/* capsule_raycast_info{capsule_feature::hemisphere, hemisphere_index} */
+       EDYNHIP_RAYCAST_FEATURE_CAPSULE_SIDE = 5,      /* capsule_raycast_info{capsule_feature::side} */
+       EDYNHIP_RAYCAST_FEATURE_POLYHEDRON_FACE = 6 }; /* polyhedron_raycast_info::face_index */
+/* flags: EDYNHIP_RAYCAST_BRUTE_FORCE (test aid): every ray tests every body with the same candidate predicate, no tree. Other flag
+ * bits: EDYNHIP_ERR_INVALID. A shard context of a multi-device world (edynhip_world_context): EDYNHIP_ERR_UNSUPPORTED. */
+enum { EDYNHIP_RAYCAST_BRUTE_FORCE = 1 };
+typedef struct {
+    uint32_t body;           /* ~0u: nothing hit (raycast_result::entity == entt::null) */
+    float fraction;          /* FLT_MAX on a miss; the point hit is lerp(p0, p1, fraction) */
+    float normal[3];         /* world-space normal */
+    int32_t feature;         /* EDYNHIP_RAYCAST_FEATURE_* */
+    uint32_t feature_index;  /* face / hemisphere index of the feature, 0 where it has none */
+    uint32_t reserved;
+} edynhip_raycast_hit;       /* 32 B */
+/* Host arrays p0[n][3], p1[n][3], ignore[num_ignore] (body indices); returns when out[n] holds the results. n = 0 is valid. */
+int edynhip_raycast(edynhip_ctx *ctx, uint32_t n, const float *p0, const float *p1, uint32_t num_ignore, const uint32_t *ignore,
+                    uint32_t flags, edynhip_raycast_hit *out);
+/* The same with DEVICE arrays: p0 / p1 hold one float4 per ray (w unused), out n records; enqueued on the context's stream,
+ * no host synchronisation (ignore is a host list, copied before the call returns). */
+int edynhip_raycast_device(edynhip_ctx *ctx, uint32_t n, const void *p0_f4, const void *p1_f4, uint32_t num_ignore, const uint32_t *ignore,
+                           uint32_t flags, void *out);
+
 /* Manifolds are kept (and returned) in ascending canonical order: key = (owner << 32) | other, where the owner is the
  * pair's procedural (dynamic) body - the one with the higher index when both are dynamic. edynhip_set_manifolds expects
  * records in that order. (EnTT's pool order is not reproducible; the solver visits manifolds in this order.) */
