@@ -2,6 +2,12 @@
 """bench.py - steps/sec of the MI355X-native Edyn stepper on the headline scene.
 
 Contract (one JSON line on rank 0):
+  plain    `python bench.py --gpus N --steps K --warmup W` does what the headline needs and nothing else: it builds and settles the scene,
+           warms up, times the K steps, writes --dump-outputs and prints the line (the headline, its config and the roofline of the
+           timed steps).
+  --full   also the legs beside the headline, each a run of its own: the other contact arithmetics, north_star and its per-rank proxy,
+           the edyn::update shim, the CPU baseline and the measured bandwidth ceilings of the roofline. A leg named explicitly
+           (--north-star NAME, --other-arithmetic-steps K > 0) runs without --full as well.
   metric   steps/sec (whole node), 32k-box pile, 10 SI iters           (BASELINE.json)
   value    pile-steps per second over all ranks, scene resident in HBM before the timed region
   state    the scene is SETTLED before anything is timed: `--settle` steps (default 120, SURVEY 8d "warm-up 120 steps") are part
@@ -12,13 +18,13 @@ Contract (one JSON line on rank 0):
            torchrun. The pile is ONE island and cannot be split: each rank steps its own replica of the pile (N islands
            sharded one per GPU, no data-path collective) and the integrated state (13 floats/body) is all-gathered over RCCL every
            step, as the registry write-back would need; value counts pile-steps, scaling = "weak".
-  north_star  (second result in the same line) north_star's own target: 1 048 576 boxes in 16 384 islands, the islands sharded
+  north_star  (--full; second result in the same line) north_star's own target: 1 048 576 boxes in 16 384 islands, the islands sharded
            over the N ranks (strong scaling of ONE scene, per-step RCCL gather of the state): bodies, steps/s, >= 60 Hz yes/no.
   roofline the SI velocity-solve kernel actually launched (edynhip_stats::solve_schedule): algorithmic bytes
            (380 B per contact point + 256 B per joint row, per iteration) / time measured with HIP events recorded
-           on the stepper's stream around that launch inside the timed region; beside the 8 TB/s spec peak the measured read
+           on the stepper's stream around that launch inside the timed region; beside the 8 TB/s spec peak (--full) the measured read
            and copy ceilings of this GPU (edynhip_measure_bandwidth).
-  cpu_baseline  Edyn's own multithreaded CPU path: the REAL reference engine (oracle/_ref/libedynref.so = the reference's
+  cpu_baseline  (--full) Edyn's own multithreaded CPU path: the REAL reference engine (oracle/_ref/libedynref.so = the reference's
            translation units compiled where they lie, driven through edyn::attach / step_simulation in
            execution_mode::sequential_multithreaded on all host cores) timed on a bounded sample of the same scene IN THE SAME
            (settled) STATE the GPU leg times, on rank 0 at N=1, in a subprocess with a wall-clock budget; next to it, in
@@ -398,15 +404,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--settle", type=int, default=None, help="settle steps before anything is timed (scene construction; default per workload: 120)")
     ap.add_argument("--workload", default="pile32k", choices=sorted(WORKLOADS))
-    ap.add_argument("--north-star", default="auto", help="workload of the north_star leg (sharded islands): a workload name, 'none', or 'auto' = islands1m on the default workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: other contact arithmetics, north_star, the edyn::update shim, the CPU baseline, "
+                         "the measured bandwidth ceilings (a plain run only builds, settles, warms up, times and prints)")
+    ap.add_argument("--north-star", default="auto", help="workload of the north_star leg (sharded islands): a workload name, 'none', or 'auto' = islands1m on the default workload with --full")
     ap.add_argument("--north-star-steps", type=int, default=60)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shim", action="store_true", help="skip the edyn::update leg (tests/cpp/bench_update: the C++ drop-in over the registry)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of a --full run")
+    ap.add_argument("--no-shim", action="store_true", help="skip the edyn::update leg of a --full run (tests/cpp/bench_update: the C++ drop-in over the registry)")
     ap.add_argument("--shim-steps", type=int, default=300)
     ap.add_argument("--arithmetic", default="reference", choices=sorted(ARITHMETIC),
                     help="contact arithmetic of the measured run (default: the reference's operations; the others are the opt-in faster forms)")
     ap.add_argument("--other-arithmetic-steps", type=int, default=None,
-                    help="timed steps of the two short legs in the OTHER contact arithmetics (config.arithmetic.steps_per_sec; default: --steps on the default workload at N=1, else 0)")
+                    help="timed steps of the two short legs in the OTHER contact arithmetics (config.arithmetic.steps_per_sec; default: --steps on the default workload at N=1 with --full, else 0)")
     ap.add_argument("--stage-timing", action="store_true",
                     help="HIP events around every stage (adds stages_ms_per_step; each event idles the GPU ~6 us, so the headline\n                    value is measured without it: only the two events around the velocity solve are recorded)")
     ap.add_argument("--cpu-sample-steps", type=int, default=6)
@@ -464,7 +473,7 @@ def main():
     finite = bool(np.isfinite(state[0]).all())
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, state, w.get_manifolds())
-    read_gbs, copy_gbs = w.measure_bandwidth(1 << 30) if rank == 0 else (0.0, 0.0)
+    read_gbs, copy_gbs = w.measure_bandwidth(1 << 30) if rank == 0 and args.full else (None, None)
 
     out = None
     state_path = None
@@ -522,9 +531,9 @@ def main():
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": (achieved / peak) if achieved is not None else None,
                          "traffic": traffic, "traffic_source": traffic_note,
                          "achieved_from_algorithmic_bytes_only": achieved_alg, "frac_from_algorithmic_bytes_only": achieved_alg / peak,
-                         "measured_read_ceiling": read_gbs, "frac_of_measured_read_ceiling": (achieved / read_gbs) if achieved is not None and read_gbs > 0 else None,
-                         "measured_copy_ceiling": copy_gbs, "frac_of_measured_copy_ceiling": (achieved / copy_gbs) if achieved is not None and copy_gbs > 0 else None,
-                         "achieved_rule": "min(algorithmic bytes, measured traffic) / kernel time; peak = HBM3E spec; the measured read-stream and device-to-device copy rates of this GPU are reported beside it",
+                         "measured_read_ceiling": read_gbs, "frac_of_measured_read_ceiling": (achieved / read_gbs) if achieved is not None and read_gbs else None,
+                         "measured_copy_ceiling": copy_gbs, "frac_of_measured_copy_ceiling": (achieved / copy_gbs) if achieved is not None and copy_gbs else None,
+                         "achieved_rule": "min(algorithmic bytes, measured traffic) / kernel time; peak = HBM3E spec; the measured read-stream and device-to-device copy rates of this GPU are reported beside it (--full)",
                          "kernel": schedule,
                          "algorithmic_bytes_per_launch": per_launch_alg,
                          "algorithmic_bytes_rule": "(380 B x contact points + 256 B x joint rows) x (velocity iterations + 1 warm-start sweep)",
@@ -546,7 +555,7 @@ def main():
             out["stages_ms_per_step"] = {k: tm[k] / steps_timed for k in ("broadphase_ms", "narrowphase_ms", "islands_ms", "colouring_ms",
                                                                          "prepare_ms", "solve_velocity_ms", "integrate_ms", "solve_position_ms",
                                                                          "finish_ms", "step_ms")}
-        if world_size == 1 and not args.no_cpu_baseline:
+        if world_size == 1 and args.full and not args.no_cpu_baseline:
             # the CPU legs start from the state the GPU leg was timed in (the first bodies of a sharded scene: its first sites)
             fd, state_path = tempfile.mkstemp(suffix=".npz", prefix="edyn_bench_state_")
             os.close(fd)
@@ -557,7 +566,7 @@ def main():
     # ---- the same workload in the other contact arithmetics (single rank): both numbers beside the headline
     other_steps = args.other_arithmetic_steps
     if other_steps is None:
-        other_steps = args.steps if (args.workload == "pile32k" and world_size == 1) else 0
+        other_steps = args.steps if (args.full and args.workload == "pile32k" and world_size == 1) else 0
     if other_steps > 0 and world_size == 1:
         for mode in ARITHMETIC:
             if mode == args.arithmetic:
@@ -573,7 +582,7 @@ def main():
     # ---- north_star: 1M bodies in 16k islands, sharded over the ranks (strong scaling), >= 60 Hz?
     ns_name = args.north_star
     if ns_name == "auto":
-        ns_name = "islands1m" if args.workload == "pile32k" else "none"
+        ns_name = "islands1m" if (args.full and args.workload == "pile32k") else "none"
     if ns_name != "none":
         if ns_name not in WORKLOADS or "shard" not in WORKLOADS[ns_name]:
             raise SystemExit(f"bench.py: --north-star {ns_name}: not a shardable workload")
@@ -598,7 +607,7 @@ def main():
         if rank == 0 and world_size == 1 and "shard" in WORKLOADS[ns_name] and WORKLOADS[ns_name]["shard_units"] >= 8:
             out["north_star"]["per_rank_proxy"] = per_rank_proxy(ns_name, args, device_index, stream, 8)
 
-    if rank == 0 and world_size == 1 and args.workload == "pile32k" and not args.no_shim:
+    if rank == 0 and world_size == 1 and args.full and args.workload == "pile32k" and not args.no_shim:
         out["shim"] = shim_leg(args.shim_steps, leg.settle)
         if "steps_per_sec" in out["shim"]:
             out["shim"]["ratio_to_value"] = {k: v / out["value"] for k, v in out["shim"]["steps_per_sec"].items()}

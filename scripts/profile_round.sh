@@ -1,13 +1,13 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): for each workload the bench line, rocprofv3 kernel-trace statistics of the same command
-# and the two HBM-traffic PMC passes, reduced to small text/json summaries under gpurun_out/ (copy into profiles/; the raw
+# Runs on the GPU box: for each workload the bench line, rocprofv3 kernel-trace statistics of the same command
+# and the two HBM-traffic PMC passes, reduced to small text/json summaries under $OUT (default out/; copy into profiles/; the raw
 # rocpd databases stay on the box). The headline workload additionally gets one step's timeline, SQ counters and a
 # --stage-timing run.
 # usage: scripts/profile_round.sh r02 [workload ...]        (default: pile32k islands256k)
 set -u
 R=${1:-r02}; shift || true
 WLS=${@:-pile32k islands256k}
-OUT=$PWD/gpurun_out
+export OUT=$(realpath -m "${OUT:-out}")
 mkdir -p $OUT
 export TMPDIR=/tmp
 for WL in $WLS; do
@@ -37,11 +37,11 @@ done
 ROUND_TAG=$R python - <<'PY'
 import glob, json, os
 out = {}
-for f in sorted(glob.glob("gpurun_out/%s_traffic_*.json" % os.environ.get("ROUND_TAG", "r04"))):
+for f in sorted(glob.glob(os.path.join(os.environ["OUT"], "%s_traffic_*.json" % os.environ.get("ROUND_TAG", "r04")))):
     try:
         j = json.load(open(f)); out[j["workload"]] = j
     except Exception:
         pass
-json.dump(out, open("gpurun_out/traffic.json", "w"), indent=1)
+json.dump(out, open(os.path.join(os.environ["OUT"], "traffic.json"), "w"), indent=1)
 PY
 ls -la $OUT | head -40

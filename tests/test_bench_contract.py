@@ -1,4 +1,5 @@
-"""bench.py prints ONE JSON line with the driver's contract keys plus roofline / cpu_baseline objects."""
+"""bench.py prints ONE JSON line with the driver's contract keys plus roofline / cpu_baseline objects (cpu_baseline and the other
+legs beside the headline with --full)."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "pile512", "--steps", "10", "--warmup", "5",
-                          "--cpu-sample-steps", "3"], capture_output=True, text=True, timeout=600)
+                          "--cpu-sample-steps", "3", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -39,6 +40,27 @@ def test_bench_json_contract():
     assert c["kind"] in ("reference", "port") and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
     if c["kind"] == "reference":   # the real engine, multithreaded: both thread counts are in the sample text
         assert c["cores"] > 1 and "1-thread" in c["sample"] and "sequential_multithreaded" in c["sample"]
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full the line carries the headline, its config and the roofline of the timed steps - none of the legs that take
+    runs of their own (other contact arithmetics, north_star, shim, CPU baseline, measured bandwidth ceilings). On the default workload,
+    where --full runs every one of them."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "5"],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 10 and d["warmup"] == 5 and d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) < 1e-9 * d["ms_per_step"]
+    assert d["unit"] == "steps/sec" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["config"]["finite"] is True
+    assert not {"cpu_baseline", "north_star", "shim"} & set(d)
+    assert list(d["config"]["arithmetic"]["steps_per_sec"]) == ["reference"]
+    r = d["roofline"]
+    assert r["measured_read_ceiling"] is None and r["measured_copy_ceiling"] is None and r["frac_from_algorithmic_bytes_only"] > 0
 
 
 def _two_rank_checks(out):
