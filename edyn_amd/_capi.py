@@ -88,6 +88,9 @@ RAYCAST_HIT_DTYPE = np.dtype([("body", np.uint32), ("fraction", np.float32), ("n
 RAYCAST_NONE, RAYCAST_BOX_FACE, RAYCAST_CYLINDER_FACE, RAYCAST_CYLINDER_SIDE_EDGE = 0, 1, 2, 3   # EDYNHIP_RAYCAST_FEATURE_*
 RAYCAST_CAPSULE_HEMISPHERE, RAYCAST_CAPSULE_SIDE, RAYCAST_POLYHEDRON_FACE = 4, 5, 6
 RAYCAST_BRUTE_FORCE = 1   # EDYNHIP_RAYCAST_BRUTE_FORCE (test aid: every ray tests every body)
+QUERY_PROCEDURAL, QUERY_NON_PROCEDURAL, QUERY_ISLANDS = 0, 1, 2   # EDYNHIP_QUERY_* categories of edynhip_query_aabb
+QUERY_CATEGORIES = {"procedural": QUERY_PROCEDURAL, "non_procedural": QUERY_NON_PROCEDURAL, "islands": QUERY_ISLANDS}
+QUERY_BRUTE_FORCE = 1     # EDYNHIP_QUERY_BRUTE_FORCE (test aid: every query tests every body / island)
 
 
 class RecordView(C.Structure):
@@ -115,7 +118,8 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_world_get_manifolds", "edynhip_world_get_stats", "edynhip_world_context", "edynhip_partition_islands",
            "edynhip_island_boxes_overlap", "edynhip_get_island_boxes",
            "edynhip_world_set_pair_filter", "edynhip_world_default_should_collide", "edynhip_get_sleep_timers", "edynhip_set_sleep_timers",
-           "edynhip_raycast", "edynhip_raycast_device"]
+           "edynhip_raycast", "edynhip_raycast_device",
+           "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats"]
 
 _lib = None
 
@@ -144,6 +148,11 @@ def lib():
         L.edynhip_get_derived.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.edynhip_raycast.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_raycast_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_query_aabb.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                         C.POINTER(C.c_uint32)]
+        L.edynhip_query_aabb_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                C.c_void_p]
+        L.edynhip_query_aabb_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.edynhip_num_manifolds.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.edynhip_get_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_set_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]

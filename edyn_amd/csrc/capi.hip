@@ -582,6 +582,7 @@ void edynhip_destroy(edynhip_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     eh::raycast_free(c);
+    eh::query_aabb_free(c);
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->idx_scratch) (void)hipFree(c->idx_scratch);
     for (void *p : c->mesh_allocs) (void)hipFree(p);

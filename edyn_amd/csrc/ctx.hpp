@@ -211,7 +211,8 @@ __host__ __device__ inline size_t pslot_at(uint32_t slot, uint32_t piece) {   //
     return (size_t)(p >> 5) * 192u + (piece << 6) + (slot & 63u);
 }
 
-struct RayTree;   // raycast.hip
+struct RayTree;   // raytree.hpp (raycast.hip, query_aabb.hip)
+struct QueryAabb;   // query_aabb.hip
 
 struct LBVH {
     uint64_t *keys = nullptr, *keys_sorted = nullptr;   // morton<<32 | body
@@ -455,6 +456,7 @@ struct edynhip_ctx {
     // raycast queries (raycast.hip): a query tree of their own, rebuilt at the first raycast after state_epoch moved on
     uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
     eh::RayTree *ray = nullptr;
+    eh::QueryAabb *qa = nullptr;   // AABB queries (query_aabb.hip): counts, scan and island boxes beside the raycast's tree
     bool world_shard = false;      // a shard of a multi-device world (multi.hip): no raycast
 };
 
@@ -486,6 +488,7 @@ int update_rotated(edynhip_ctx *c);
 int build_query_tree(edynhip_ctx *c, const uint32_t *list, uint32_t n, const float4 *amin, const float4 *amax, Counters *cnt,
                      uint64_t *keys, uint64_t *keys_sorted, uint32_t *parent, uint32_t *left, uint32_t *right, uint32_t *visit, uint32_t *rope);
 void raycast_free(edynhip_ctx *c);   // raycast.hip
+void query_aabb_free(edynhip_ctx *c);   // query_aabb.hip
 }  // namespace eh
 
 #define EH_HIP(c, call)                                                          \

@@ -14,35 +14,16 @@
 #include "ctx.hpp"
 #include "dpolyhedron.hpp"
 #include "draycast.hpp"
+#include "raytree.hpp"
 #include <algorithm>
 #include <cstring>
 
 namespace eh {
 using namespace dm;
 
-constexpr float kFatInset = 0.1f;             // dynamic_tree::aabb_inset = -0.1 (dynamic_tree.hpp:24, dynamic_tree.cpp:45)
 constexpr float kNodeGrow = 1e-5f;            // relative growth of internal node boxes and of the ray's tolerance (see above)
-constexpr uint32_t kLeafBit = 0x80000000u;    // nmin.w of a leaf: kLeafBit | body; of an internal node: its left child
-constexpr uint32_t kRayEnd = 0xFFFFFFFFu;     // rope of the last node of a depth-first walk (broadphase.hip kRopeEnd)
 constexpr uint32_t kNoBody = 0xFFFFFFFFu;
 constexpr uint32_t kChunk = 1u << 20;          // rays per launch (and per staging buffer of the host entry point)
-
-struct RayTree {
-    uint32_t cap = 0;
-    uint64_t epoch = 0;               // edynhip_ctx::state_epoch the boxes and the tree were built for (0: never)
-    uint32_t n_tree = 0, n_planes = 0;
-    float4 *org = nullptr, *amin = nullptr, *amax = nullptr;   // [cap] shape frame and AABB from the current transforms
-    uint32_t *list = nullptr;         // [cap] tree bodies (ascending), then the planes
-    uint64_t *keys = nullptr, *keys_sorted = nullptr;          // [cap]
-    uint32_t *parent = nullptr, *left = nullptr, *right = nullptr, *visit = nullptr, *rope = nullptr;   // [2 cap]
-    float4 *nmin = nullptr, *nmax = nullptr;                   // [2 cap] node records: (min, left child | leaf body), (max, rope)
-    Counters *cnt = nullptr;          // Morton bounds of this tree
-    uint32_t *mask = nullptr;         // [cap / 32 + 1] ignore bits of the current call
-    float4 *stage = nullptr;          // host entry point: p0 [kChunk], p1 [kChunk], out [2 kChunk]
-    std::vector<void *> allocs;
-    std::vector<uint32_t> host_list, host_mask;
-    std::vector<float4> host_pts;
-};
 
 void raycast_free(edynhip_ctx *c) {
     if (!c->ray) return;
@@ -280,6 +261,12 @@ static int prepare(edynhip_ctx *c, uint32_t num_ignore, const uint32_t *ignore, 
         EH_HIP(c, hipMemcpyAsync(t.mask, t.host_mask.data(), t.host_mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
     return EDYNHIP_OK;
+}
+
+// query_aabb.hip walks the same tree: boxes and tree brought up to date, no ignore bits.
+int query_tree_prepare(edynhip_ctx *c) {
+    bool use_mask = false;
+    return prepare(c, 0, nullptr, use_mask);
 }
 
 static RayArgs ray_args(edynhip_ctx *c, bool use_mask, uint32_t flags) {

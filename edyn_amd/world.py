@@ -465,6 +465,35 @@ class World:
         self._check(self._L.edynhip_raycast_device(self._h, int(n), C.c_void_p(p0_ptr), C.c_void_p(p1_ptr), len(ign),
                                                    _ptr(ign) if len(ign) else None, flags, C.c_void_p(out_ptr)))
 
+    # ---- AABB queries: edyn::query_procedural_aabb / query_non_procedural_aabb / query_island_aabb (collision/query_aabb.hpp) for batches
+    def query_aabb(self, boxes, category="procedural", brute_force=False):
+        """Boxes (n, 6) = (min, max), or one box of shape (6,). Returns (offsets[n + 1], ids): ids[offsets[i]:offsets[i + 1]] are the bodies
+        (category "procedural" / "non_procedural") or island labels ("islands") whose box grown by 0.1 meets box i, in ascending order."""
+        b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 6))
+        cat = _capi.QUERY_CATEGORIES[category] if isinstance(category, str) else int(category)
+        flags = _capi.QUERY_BRUTE_FORCE if brute_force else 0
+        offsets = np.zeros(len(b) + 1, np.uint32)
+        total = C.c_uint32(0)
+        self._check(self._L.edynhip_query_aabb(self._h, cat, len(b), _ptr(b), flags, _ptr(offsets), None, 0, C.byref(total)))
+        ids = np.zeros(total.value, np.uint32)
+        if total.value:   # (sized by the count: a second call, which cannot run out of capacity)
+            self._check(self._L.edynhip_query_aabb(self._h, cat, len(b), _ptr(b), flags, _ptr(offsets), _ptr(ids), len(ids), C.byref(total)))
+        return offsets, ids
+
+    def query_aabb_device(self, n, boxes_ptr, offsets_ptr, ids_ptr, capacity, total_ptr, category="procedural", brute_force=False):
+        """Device pointers: boxes hold 2 n float4 (min, max; w unused), offsets n + 1 uint32, ids `capacity` uint32 (0 / None: count only),
+        total one uint32; enqueued on the context's stream. Nothing is written at or beyond `capacity`."""
+        cat = _capi.QUERY_CATEGORIES[category] if isinstance(category, str) else int(category)
+        flags = _capi.QUERY_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_query_aabb_device(self._h, cat, int(n), C.c_void_p(boxes_ptr), flags, C.c_void_p(offsets_ptr),
+                                                      C.c_void_p(ids_ptr) if ids_ptr else None, int(capacity), C.c_void_p(total_ptr)))
+
+    def query_aabb_stats(self):
+        """(queries whose hits a wave sorted, queries whose hits a wave packed from the body range) since the world was created."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.edynhip_query_aabb_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def get_manifolds(self):
         m = C.c_uint32(0)
         self._check(self._L.edynhip_num_manifolds(self._h, C.byref(m)))

@@ -1546,6 +1546,80 @@ inline std::vector<raycast_result> raycast(entt::registry &registry, const std::
     return out;
 }
 
+// ---- collision/query_aabb.hpp:10-46: AABB queries, answered on the device (edynhip_query_aabb; definition: DESIGN §8 "AABB queries").
+// Hits are the bodies whose AABB grown by 0.1 meets the box; func is called once per hit, in ascending order of creation (the reference
+// calls in its tree's visit order). Island entities do not exist in this stepper, so query_island_aabb is not offered (island queries:
+// edynhip_query_aabb with EDYNHIP_QUERY_ISLANDS, by label).
+struct query_aabb_result {
+    std::vector<entt::entity> procedural_entities;
+    std::vector<entt::entity> non_procedural_entities;
+    std::vector<entt::entity> island_entities;
+};
+using query_aabb_id_type = unsigned;
+#if __has_include(<entt/entt.hpp>)
+using query_aabb_delegate_type = entt::delegate<void(query_aabb_id_type, const query_aabb_result &)>;   // (the bundled mini registry has no delegate)
+#endif
+namespace detail {
+inline void query_aabb_prepare(entt::registry &registry, gpu_stepper &s, const char *who) {
+    if (s.cfg.execution_mode == execution_mode::asynchronous)
+        throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": not in execution_mode::asynchronous (the reference asks for query_aabb_async there, which this stepper does not provide)").c_str());
+    if (s.multi()) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": a world over several devices (init_config::devices) has no AABB query").c_str());
+    sync_removed(registry, s);
+    if (s.scene_dirty) upload_scene(registry, s);
+    if (s.state_dirty) upload_state(registry, s);
+}
+// func(query index, entity) for every hit of every box, by query and ascending body index: one launch and one synchronisation per pass
+template <typename Func>
+inline void query_aabb_batch(entt::registry &registry, int category, const AABB *boxes, size_t n, Func &&func, const char *who) {
+    auto &s = registry.ctx().get<gpu_stepper>();
+    query_aabb_prepare(registry, s, who);
+    if (!s.ctx || s.bodies.empty() || n == 0) return;
+    std::vector<float> b(6 * n);
+    for (size_t i = 0; i < n; ++i) {
+        b[6 * i] = boxes[i].min.x; b[6 * i + 1] = boxes[i].min.y; b[6 * i + 2] = boxes[i].min.z;
+        b[6 * i + 3] = boxes[i].max.x; b[6 * i + 4] = boxes[i].max.y; b[6 * i + 5] = boxes[i].max.z;
+    }
+    std::vector<uint32_t> offsets(n + 1), ids;
+    uint32_t total = 0;
+    check(s, edynhip_query_aabb(s.ctx, category, (uint32_t)n, b.data(), 0, offsets.data(), nullptr, 0, &total));
+    if (total == 0) return;
+    ids.resize(total);
+    check(s, edynhip_query_aabb(s.ctx, category, (uint32_t)n, b.data(), 0, offsets.data(), ids.data(), total, &total));
+    for (size_t i = 0; i < n; ++i)
+        for (uint32_t k = offsets[i]; k < offsets[i + 1]; ++k)
+            if (ids[k] < s.bodies.size() && s.bodies[ids[k]] != entt::null) func(i, s.bodies[ids[k]]);
+}
+}  // namespace detail
+/// edyn::query_procedural_aabb (collision/query_aabb.hpp:10-14, broadphase.hpp:81-86): func(entity) for every dynamic body in the box.
+template <typename Func>
+inline void query_procedural_aabb(entt::registry &registry, const AABB &aabb, Func func) {
+    detail::query_aabb_batch(registry, EDYNHIP_QUERY_PROCEDURAL, &aabb, 1, [&](size_t, entt::entity e) { func(e); }, "edyn::query_procedural_aabb");
+}
+/// edyn::query_non_procedural_aabb (collision/query_aabb.hpp:16-20, broadphase.hpp:88-93): static and kinematic bodies, planes included.
+template <typename Func>
+inline void query_non_procedural_aabb(entt::registry &registry, const AABB &aabb, Func func) {
+    detail::query_aabb_batch(registry, EDYNHIP_QUERY_NON_PROCEDURAL, &aabb, 1, [&](size_t, entt::entity e) { func(e); }, "edyn::query_non_procedural_aabb");
+}
+/// Extensions (not in the reference): a batch of boxes in one call; func(query index, entity).
+template <typename Func>
+inline void query_procedural_aabb(entt::registry &registry, const std::vector<AABB> &aabbs, Func func) {
+    detail::query_aabb_batch(registry, EDYNHIP_QUERY_PROCEDURAL, aabbs.data(), aabbs.size(), func, "edyn::query_procedural_aabb");
+}
+template <typename Func>
+inline void query_non_procedural_aabb(entt::registry &registry, const std::vector<AABB> &aabbs, Func func) {
+    detail::query_aabb_batch(registry, EDYNHIP_QUERY_NON_PROCEDURAL, aabbs.data(), aabbs.size(), func, "edyn::query_non_procedural_aabb");
+}
+/// collision/query_aabb.hpp:37-44: the asynchronous queries belong to execution_mode::asynchronous's worker, which this stepper does not
+/// have; they are declared for source compatibility and throw stepper_error in every mode.
+template <typename Delegate>
+inline query_aabb_id_type query_aabb_async(entt::registry &, const AABB &, const Delegate &, bool, bool, bool) {
+    throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::query_aabb_async: not provided (use query_procedural_aabb / query_non_procedural_aabb in a sequential mode)");
+}
+template <typename Delegate>
+inline query_aabb_id_type query_aabb_of_interest_async(entt::registry &, const AABB &, const Delegate &) {
+    throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::query_aabb_of_interest_async: not provided (use query_procedural_aabb / query_non_procedural_aabb in a sequential mode)");
+}
+
 // ---- util/rigidbody.hpp:84-93, rigidbody.cpp:47-191
 inline void make_rigidbody(entt::entity entity, entt::registry &registry, const rigidbody_def &def) {
     auto &s = registry.ctx().get<detail::gpu_stepper>();

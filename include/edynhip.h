@@ -308,6 +308,45 @@ int edynhip_raycast(edynhip_ctx *ctx, uint32_t n, const float *p0, const float *
 int edynhip_raycast_device(edynhip_ctx *ctx, uint32_t n, const void *p0_f4, const void *p1_f4, uint32_t num_ignore, const uint32_t *ignore,
                            uint32_t flags, void *out);
 
+/* edyn::query_procedural_aabb / query_non_procedural_aabb / query_island_aabb (include/edyn/collision/query_aabb.hpp:10-26,
+ * include/edyn/collision/broadphase.hpp:81-100, src/edyn/collision/dynamic_tree.cpp query) for a batch of boxes q = (min, max).
+ * Candidates by category:
+ *   EDYNHIP_QUERY_PROCEDURAL      every body that has a shape, is not removed and is dynamic (the holders of procedural_tag);
+ *   EDYNHIP_QUERY_NON_PROCEDURAL  every shaped, not removed body that is static or kinematic, planes (with their half-space box) included;
+ *   EDYNHIP_QUERY_ISLANDS         every island (label = its lowest body index, as edynhip_get_derived returns it) with the union of the
+ *                                 boxes of its shaped dynamic bodies.
+ * A candidate is reported iff intersect_aabb(q.min, q.max, box.min - 0.1, box.max + 0.1) (include/edyn/comp/aabb.hpp:45-47,
+ * src/edyn/math/geom.cpp:762-770: six <= / >= comparisons on closed intervals; 0.1 is dynamic_tree::aabb_inset, dynamic_tree.hpp:24,
+ * dynamic_tree.cpp:45) - the box a freshly created leaf of the reference's tree holds. (The reference's fat boxes depend on the history
+ * of dynamic_tree::move; on leaves just created the two coincide exactly.) Sleeping bodies are reported; amorphous and removed bodies
+ * never are. The six comparisons are evaluated as written and nothing else: a box that only touches is a hit, a NaN in the query reports
+ * nothing, and an inverted query (min > max on an axis) is not special - it reports what the formula passes, as the reference's tree does.
+ * The one intended difference: the reference reports in tree-visit order, here each query's hits are in ASCENDING body index (island
+ * label). The queries see the context's current state (the last step, or edynhip_set_state / edynhip_add_bodies ... since) through the
+ * raycast's query tree, rebuilt at the first query after a change; a query changes nothing a later step computes.
+ * Result (CSR): offsets[n + 1] (offsets[0] = 0, offsets[n] = *total), ids[offsets[i] .. offsets[i + 1]) the hits of query i. offsets and
+ * *total are always complete (saturated at 0xFFFFFFFF). flags: EDYNHIP_QUERY_BRUTE_FORCE (test aid): every query tests every body /
+ * island with the same predicate, no tree. Unknown category or flag bits: EDYNHIP_ERR_INVALID. A shard context of a multi-device world
+ * (edynhip_world_context): EDYNHIP_ERR_UNSUPPORTED. n = 0 is valid. */
+enum { EDYNHIP_QUERY_PROCEDURAL = 0, EDYNHIP_QUERY_NON_PROCEDURAL = 1, EDYNHIP_QUERY_ISLANDS = 2 };
+enum { EDYNHIP_QUERY_BRUTE_FORCE = 1 };
+/* Host arrays: boxes6[n][6] (min, max); offsets[n + 1]; ids[capacity], may be NULL (count only). *total > capacity: returns
+ * EDYNHIP_ERR_CAPACITY with offsets / *total valid and ids unspecified (size ids by *total and ask again). */
+int edynhip_query_aabb(edynhip_ctx *ctx, int category, uint32_t n, const float *boxes6, uint32_t flags,
+                       uint32_t *offsets, uint32_t *ids, uint32_t capacity, uint32_t *total);
+/* The same with DEVICE arrays: boxes as 2 float4 per query (min, max; w unused), offsets n + 1 uint32, ids capacity uint32 (may be NULL),
+ * total 1 uint32; enqueued on the context's stream, no host synchronisation. No id is written at or beyond `capacity`: when
+ * *total > capacity the ids of the queries that did not fit are incomplete, offsets and *total are still right. */
+int edynhip_query_aabb_device(edynhip_ctx *ctx, int category, uint32_t n, const void *boxes_f4, uint32_t flags,
+                              void *offsets, void *ids, uint32_t capacity, void *total);
+/* Statistics since the context was created, counted by the fill kernels: segments one wave sorted in LDS, and queries whose hits one
+ * wave packed from the body range (the second fill path of large results); every other query was filled and sorted by its own lane.
+ * Calls that only count (ids = NULL, or EDYNHIP_ERR_CAPACITY) add nothing. Either pointer may be NULL.
+ * Debug knob: the environment variable EDYNHIP_QUERY_SCAN_RATIO = r (read when a context answers its first query) moves the switch to
+ * the second fill path to "more than num_bodies / r hits" (default 64). It changes the cost only, never a result; it exists for
+ * scripts/bench_query_aabb.py --ratios and for tests that steer queries onto one path. */
+int edynhip_query_aabb_stats(edynhip_ctx *ctx, uint64_t *wave_sorted, uint64_t *wave_filled);
+
 /* Manifolds are kept (and returned) in ascending canonical order: key = (owner << 32) | other, where the owner is the
  * pair's procedural (dynamic) body - the one with the higher index when both are dynamic. edynhip_set_manifolds expects
  * records in that order. (EnTT's pool order is not reproducible; the solver visits manifolds in this order.) */
