@@ -119,7 +119,8 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_island_boxes_overlap", "edynhip_get_island_boxes",
            "edynhip_world_set_pair_filter", "edynhip_world_default_should_collide", "edynhip_get_sleep_timers", "edynhip_set_sleep_timers",
            "edynhip_raycast", "edynhip_raycast_device",
-           "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats"]
+           "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats",
+           "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device"]
 
 _lib = None
 
@@ -220,6 +221,12 @@ def lib():
         L.edynhip_world_get_stats.argtypes = [C.c_void_p, C.POINTER(WorldStats)]
         L.edynhip_world_context.restype = C.c_void_p
         L.edynhip_world_context.argtypes = [C.c_void_p, C.c_uint32]
+        L.edynhip_world_raycast.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_world_raycast_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_world_query_aabb.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.POINTER(C.c_uint32)]
+        L.edynhip_world_query_aabb_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                      C.c_void_p]
         L.edynhip_partition_islands.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_island_boxes_overlap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_get_island_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]

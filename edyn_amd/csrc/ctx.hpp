@@ -457,7 +457,14 @@ struct edynhip_ctx {
     uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
     eh::RayTree *ray = nullptr;
     eh::QueryAabb *qa = nullptr;   // AABB queries (query_aabb.hip): counts, scan and island boxes beside the raycast's tree
-    bool world_shard = false;      // a shard of a multi-device world (multi.hip): no raycast
+    bool world_shard = false;      // a shard of a multi-device world (multi.hip): the public queries are refused, the world asks through shard_*
+    // Queries on a multi-device world (multi.hip edynhip_world_raycast / edynhip_world_query_aabb): every body is answered by exactly one
+    // shard. answers: device bit per local body this context answers for (nullptr: all of them), host_answers its host copy (empty: all);
+    // query_island: island labels carried through a re-partition, read by the island category until this context's first step recomputes
+    // b.island. The device arrays are the world's (Shard), set by eh::shard_set_answers.
+    const uint32_t *answers = nullptr;
+    std::vector<uint32_t> host_answers;
+    const uint32_t *query_island = nullptr;
 };
 
 namespace eh {
@@ -489,6 +496,14 @@ int build_query_tree(edynhip_ctx *c, const uint32_t *list, uint32_t n, const flo
                      uint64_t *keys, uint64_t *keys_sorted, uint32_t *parent, uint32_t *left, uint32_t *right, uint32_t *visit, uint32_t *rope);
 void raycast_free(edynhip_ctx *c);   // raycast.hip
 void query_aabb_free(edynhip_ctx *c);   // query_aabb.hip
+// what a multi-device world asks of a shard context (the public entry points refuse one): device arrays on the context's device, local
+// body indices, everything enqueued on the context's stream
+void shard_set_answers(edynhip_ctx *c, const uint32_t *answers_dev, std::vector<uint32_t> host_bits, const uint32_t *query_island_dev);
+int shard_raycast(edynhip_ctx *c, uint32_t n, const void *p0_f4, const void *p1_f4, uint32_t num_ignore, const uint32_t *ignore, uint32_t flags, void *out);   // raycast.hip
+// query_aabb.hip: the count pass (counts, 64-bit total and offsets in the context's own buffers: *cnt, *offsets, *tot64 point at them) and the
+// fill pass of the queries counted last (ids[capacity] on this device)
+int shard_query_count(edynhip_ctx *c, int category, uint32_t n, const void *boxes_f4, uint32_t flags, const uint32_t **cnt, const uint32_t **offsets, const unsigned long long **tot64);
+int shard_query_fill(edynhip_ctx *c, int category, uint32_t n, const void *boxes_f4, uint32_t flags, uint32_t *ids, uint32_t capacity);
 }  // namespace eh
 
 #define EH_HIP(c, call)                                                          \

@@ -20,6 +20,7 @@
 // their relative order: a shard computes for its islands exactly what one context computes for the whole world
 // (tests/cpp/multi.cpp: bit-equal through a forced and an approach-triggered re-partition).
 #include "ctx.hpp"
+#include "world_query.hpp"
 #include <chrono>
 #include <algorithm>
 #include <atomic>
@@ -236,6 +237,17 @@ struct HostScene {   // deep copy of what the caller described, in global indice
     std::vector<Mesh> meshes;
 };
 
+struct DevBuf { void *p = nullptr; size_t cap = 0; };   // a device buffer that only grows (the caller has set the device)
+hipError_t dev_grow(DevBuf &b, size_t bytes) {
+    if (bytes <= b.cap) return hipSuccess;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipSuccess) b.cap = bytes;
+    return e;
+}
+void dev_free(DevBuf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+
 struct Shard {
     edynhip_ctx *ctx = nullptr;
     int device = 0;
@@ -252,6 +264,15 @@ struct Shard {
     // collected for a re-partition
     std::vector<uint32_t> labels; std::vector<float> aabb; std::vector<edynhip_manifold> manifolds; std::vector<float> imp24, imp10; std::vector<uint8_t> asleep;
     std::vector<uint32_t> sleep_label; std::vector<double> sleep_since; double sleep_clock = 0;
+    // queries (edynhip_world_raycast / edynhip_world_query_aabb). Per context, [cap]: local_ids on the device, the bit per local body this
+    // shard answers for, island labels carried through a re-partition. Scratch: the queries and the local results of a shard that is not on
+    // the home device, the hit lists of any shard; the last count pass (the context's buffers) and its 64-bit total (pinned).
+    uint32_t *ids_dev = nullptr, *ans_dev = nullptr, *qisl_dev = nullptr;
+    DevBuf q_in, q_out, q_ids;
+    std::vector<uint32_t> q_ignore;
+    const void *q_boxes = nullptr;
+    const uint32_t *q_cnt = nullptr, *q_off = nullptr;
+    unsigned long long *q_tot = nullptr;
 };
 
 class Pool {   // one persistent host thread per shard (a context is single-threaded; its step spins on its own counters)
@@ -327,6 +348,13 @@ struct edynhip_world {
     edynhip_world_stats stats{};
     std::string err;
     int fail(int code, const std::string &what) { err = what; return code; }
+    // queries: the home device is devices[0]; a stream of the world's own there, the shards' answers side by side, the scan's scratch, and
+    // the device copies of the host entry points' arrays
+    hipStream_t qstream = nullptr;
+    DevBuf h_hits, h_cnt, h_off, h_ids, h_scan, h_in, h_out, h_off_out, h_ids_out;
+    unsigned long long *q_pin = nullptr;           // pinned: the 64-bit total of the last count
+    std::vector<uint32_t> query_labels;            // island labels (global) of the state the shards were last rebuilt from
+    std::vector<float4> q_stage;
 };
 
 namespace {
@@ -345,8 +373,14 @@ void free_shard(Shard &s) {
     if (s.pack_host) (void)hipHostFree(s.pack_host);
     if (s.mon_dev) (void)hipFree(s.mon_dev);
     if (s.mon_host) (void)hipHostFree(s.mon_host);
+    if (s.ids_dev) (void)hipFree(s.ids_dev);
+    if (s.ans_dev) (void)hipFree(s.ans_dev);
+    if (s.qisl_dev) (void)hipFree(s.qisl_dev);
+    if (s.q_tot) (void)hipHostFree(s.q_tot);
+    dev_free(s.q_in); dev_free(s.q_out); dev_free(s.q_ids);
     if (s.ctx) edynhip_destroy(s.ctx);
     s.ctx = nullptr; s.pack_dev = s.pack_host = nullptr; s.mon_dev = s.mon_host = nullptr;
+    s.ids_dev = s.ans_dev = s.qisl_dev = nullptr; s.q_tot = nullptr; s.q_cnt = s.q_off = nullptr; s.q_boxes = nullptr;
     s.cap = s.joint_cap = s.meshes_created = 0;
 }
 
@@ -384,6 +418,7 @@ struct Carry {   // what travels with the islands through a re-partition (global
     // island boxes of the state the shards are built from, owners = the new partition: the approach check after the rebuild sweeps these
     // (thousands) instead of every body's box (hundreds of thousands)
     std::vector<IslandBox> island_boxes;
+    std::vector<uint32_t> island;              // per global body: its island label at the re-partition (what the island query reports until the next step)
 };
 
 int shard_filter_thunk(void *user, uint32_t body, uint32_t other) {
@@ -449,7 +484,7 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
         int status = 0;
         s.ctx = edynhip_create(&cfg, &status);
         if (!s.ctx) { s.rc = status; s.err = edynhip_last_error(nullptr); return; }
-        s.ctx->world_shard = true;   // (raycast.hip: a shard holds part of a world; raycasts on worlds are not provided)
+        s.ctx->world_shard = true;   // (the public queries refuse a shard: it holds part of a world, which answers through edynhip_world_raycast / _query_aabb)
         s.cap = cfg.max_bodies; s.joint_cap = cfg.max_joints;
         trace.mark("edynhip_create");
         for (const HostScene::Mesh &m : sc.meshes) {
@@ -547,8 +582,33 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
         SH_HIP(s, hipHostMalloc((void **)&s.pack_host, (size_t)std::max<uint32_t>(s.cap, 1) * 13 * sizeof(float), hipHostMallocDefault));
         SH_HIP(s, hipMalloc((void **)&s.mon_dev, words * sizeof(uint32_t)));
         SH_HIP(s, hipHostMalloc((void **)&s.mon_host, (2 + 7 * (size_t)s.cap) * sizeof(uint32_t), hipHostMallocDefault));
+        SH_HIP(s, hipMalloc((void **)&s.ids_dev, (size_t)std::max<uint32_t>(s.cap, 1) * sizeof(uint32_t)));
+        SH_HIP(s, hipMalloc((void **)&s.ans_dev, ((size_t)s.cap / 32 + 1) * sizeof(uint32_t)));
+        SH_HIP(s, hipMalloc((void **)&s.qisl_dev, (size_t)std::max<uint32_t>(s.cap, 1) * sizeof(uint32_t)));
+        SH_HIP(s, hipHostMalloc((void **)&s.q_tot, sizeof(unsigned long long), hipHostMallocDefault));
     }
     SH_HIP(s, hipMemset(s.mon_dev, 0, words * sizeof(uint32_t)));
+    // queries: every body is answered by one shard - the bodies whose state this shard reports (shard 0: the replicated ones too)
+    {
+        std::vector<uint32_t> bits;
+        if (r != 0) {
+            bits.assign((size_t)nl / 32 + 1, 0u);
+            for (uint32_t l : s.owned_local) bits[l >> 5] |= 1u << (l & 31u);
+            SH_HIP(s, hipMemcpy(s.ans_dev, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        if (nl) SH_HIP(s, hipMemcpy(s.ids_dev, s.local_ids.data(), (size_t)nl * sizeof(uint32_t), hipMemcpyHostToDevice));
+        const bool labels = carry.any && carry.island.size() == n && nl;
+        if (labels) {   // (an island lives on one shard: its label is local)
+            std::vector<uint32_t> lab(nl);
+            for (uint32_t l = 0; l < nl; ++l) {
+                const uint32_t g = s.local_ids[l], root = carry.island[g];
+                const int32_t lr = w->rank_of[g] == (int32_t)r && root < n ? s.to_local[root] : -1;
+                lab[l] = lr >= 0 ? (uint32_t)lr : l;
+            }
+            SH_HIP(s, hipMemcpy(s.qisl_dev, lab.data(), (size_t)nl * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        shard_set_answers(s.ctx, r != 0 ? s.ans_dev : nullptr, std::move(bits), labels ? s.qisl_dev : nullptr);
+    }
     trace.mark("warm start, sleep state, gather / monitor buffers");
 }
 
@@ -753,6 +813,15 @@ int repartition(edynhip_world *w, bool sticky) {
             }
         }
     }
+    // the island query's labels: a shard that has not stepped since it was rebuilt still answers with the labels it was rebuilt with
+    carry.island = labels;
+    if (w->query_labels.size() == n)
+        for (uint32_t r = 0; r < W; ++r) {
+            const Shard &s = w->shards[r];
+            if (!s.ctx || !s.ctx->query_island || s.ctx->step_index != 0) continue;
+            for (uint32_t g : s.local_ids) if (w->rank_of[g] == (int32_t)r) carry.island[g] = w->query_labels[g];
+        }
+    w->query_labels = carry.island;
     // what travels with the bodies of the shards read in full (all of them / later: the ones that change)
     auto take_heavy = [&](const std::vector<uint8_t> *only) {
         for (uint32_t r = 0; r < W; ++r) {
@@ -1067,6 +1136,10 @@ edynhip_world *edynhip_world_create(const edynhip_config *cfg, const int32_t *de
 void edynhip_world_destroy(edynhip_world *w) {
     if (!w) return;
     for (Shard &s : w->shards) free_shard(s);
+    if (!w->devices.empty()) (void)hipSetDevice(w->devices[0]);
+    if (w->qstream) { (void)hipStreamSynchronize(w->qstream); (void)hipStreamDestroy(w->qstream); }
+    for (DevBuf *b : {&w->h_hits, &w->h_cnt, &w->h_off, &w->h_ids, &w->h_scan, &w->h_in, &w->h_out, &w->h_off_out, &w->h_ids_out}) dev_free(*b);
+    if (w->q_pin) (void)hipHostFree(w->q_pin);
     delete w;
 }
 
@@ -1234,6 +1307,264 @@ int edynhip_world_get_stats(edynhip_world *w, edynhip_world_stats *out) {
 edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard) {
     if (!w || shard >= w->shards.size() || ensure_built(w) != EDYNHIP_OK) return nullptr;
     return w->shards[shard].ctx;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ queries on the world
+// Every shard answers for its own bodies with the single context's kernels (eh::shard_raycast / shard_query_*), on its pool thread and
+// its context's stream; local indices become global ones on the shard's device; the answers meet on the home device (devices[0]),
+// where world_query.hip merges them into what ONE context holding the whole scene returns. A shard on the home device reads the
+// caller's arrays and writes its answer in place; any other shard's queries and answers travel device to device.
+namespace {
+
+#define W_HIP(w, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return (w)->fail(EDYNHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
+constexpr uint32_t kWorldChunk = 1u << 20;   // rays per pass (raycast.hip kChunk)
+constexpr unsigned long long kSat32 = 0xFFFFFFFFull;
+
+int query_begin(edynhip_world *w) {
+    EH_TRY(ensure_built(w));
+    W_HIP(w, hipSetDevice(w->devices[0]));
+    if (!w->qstream) W_HIP(w, hipStreamCreateWithFlags(&w->qstream, hipStreamNonBlocking));
+    if (!w->q_pin) W_HIP(w, hipHostMalloc((void **)&w->q_pin, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    return EDYNHIP_OK;
+}
+
+// the shards that hold bodies, and each one's slot among them
+uint32_t active_slots(const edynhip_world *w, std::vector<int32_t> &slot) {
+    uint32_t k = 0;
+    slot.assign(w->shards.size(), -1);
+    for (uint32_t r = 0; r < w->shards.size(); ++r) if (w->shards[r].ctx && !w->shards[r].local_ids.empty()) slot[r] = (int32_t)k++;
+    return k;
+}
+
+// m <= kWorldChunk rays, arrays on the home device
+int world_raycast_chunk(edynhip_world *w, uint32_t m, const float4 *p0, const float4 *p1, uint32_t num_ignore, const uint32_t *ignore, uint32_t flags, void *out) {
+    const int home = w->devices[0];
+    std::vector<int32_t> slot;
+    const uint32_t A = active_slots(w, slot);
+    W_HIP(w, hipSetDevice(home));
+    W_HIP(w, dev_grow(w->h_hits, (size_t)std::max(A, 1u) * m * sizeof(edynhip_raycast_hit)));
+    w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        if (slot[r] < 0 || s.rc != EDYNHIP_OK) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        hipStream_t st = s.ctx->stream;
+        const uint32_t nl = (uint32_t)s.local_ids.size();
+        uint8_t *dst = (uint8_t *)w->h_hits.p + (size_t)slot[r] * m * sizeof(edynhip_raycast_hit);
+        const void *a = p0, *b = p1;
+        void *o = dst;
+        if (s.device != home) {
+            SH_HIP(s, dev_grow(s.q_in, 2 * (size_t)m * sizeof(float4)));
+            SH_HIP(s, dev_grow(s.q_out, (size_t)m * sizeof(edynhip_raycast_hit)));
+            SH_HIP(s, hipMemcpyPeerAsync(s.q_in.p, s.device, p0, home, (size_t)m * sizeof(float4), st));
+            SH_HIP(s, hipMemcpyPeerAsync((float4 *)s.q_in.p + m, s.device, p1, home, (size_t)m * sizeof(float4), st));
+            a = s.q_in.p; b = (const float4 *)s.q_in.p + m; o = s.q_out.p;
+        }
+        s.q_ignore.clear();
+        for (uint32_t k = 0; k < num_ignore; ++k)
+            if (ignore[k] < w->scene.n && s.to_local[ignore[k]] >= 0) s.q_ignore.push_back((uint32_t)s.to_local[ignore[k]]);
+        SH_TRY(s, shard_raycast(s.ctx, m, a, b, (uint32_t)s.q_ignore.size(), s.q_ignore.data(), flags, o));
+        wq_translate_hits(st, m, o, s.ids_dev, nl);
+        SH_HIP(s, hipGetLastError());
+        if (s.device != home) SH_HIP(s, hipMemcpyPeerAsync(dst, home, o, s.device, (size_t)m * sizeof(edynhip_raycast_hit), st));
+        SH_HIP(s, hipStreamSynchronize(st));
+    });
+    EH_TRY(shard_error(w));
+    W_HIP(w, hipSetDevice(home));
+    wq_rc_merge(w->qstream, A, m, w->h_hits.p, m, out);
+    W_HIP(w, hipGetLastError());
+    W_HIP(w, hipStreamSynchronize(w->qstream));   // (the shards' answers are overwritten by the next pass)
+    return EDYNHIP_OK;
+}
+
+// The count pass: offsets [n + 1] and total [1] on the home device; the 64-bit total in *tot. The shards keep their counts and lists for
+// world_query_fill.
+int world_query_count(edynhip_world *w, int category, uint32_t n, const float4 *boxes, uint32_t flags, uint32_t *offsets, uint32_t *total, unsigned long long *tot) {
+    const int home = w->devices[0];
+    std::vector<int32_t> slot;
+    const uint32_t A = n ? active_slots(w, slot) : 0u;
+    W_HIP(w, hipSetDevice(home));
+    W_HIP(w, dev_grow(w->h_cnt, (size_t)std::max(A, 1u) * std::max(n, 1u) * sizeof(uint32_t)));
+    if (A) w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        if (slot[r] < 0 || s.rc != EDYNHIP_OK) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        hipStream_t st = s.ctx->stream;
+        s.q_boxes = boxes;
+        if (s.device != home) {
+            SH_HIP(s, dev_grow(s.q_in, 2 * (size_t)n * sizeof(float4)));
+            SH_HIP(s, hipMemcpyPeerAsync(s.q_in.p, s.device, boxes, home, 2 * (size_t)n * sizeof(float4), st));
+            s.q_boxes = s.q_in.p;
+        }
+        const unsigned long long *t64 = nullptr;
+        SH_TRY(s, shard_query_count(s.ctx, category, n, s.q_boxes, flags, &s.q_cnt, &s.q_off, &t64));
+        SH_HIP(s, hipMemcpyAsync(s.q_tot, t64, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        if (s.device != home)
+            SH_HIP(s, hipMemcpyPeerAsync((uint32_t *)w->h_cnt.p + (size_t)slot[r] * n, home, s.q_cnt, s.device, (size_t)n * sizeof(uint32_t), st));
+        SH_HIP(s, hipStreamSynchronize(st));
+    });
+    EH_TRY(shard_error(w));
+    WqShards sh{};
+    sh.W = A;
+    for (uint32_t r = 0; r < w->shards.size() && A; ++r)
+        if (slot[r] >= 0) sh.cnt[slot[r]] = w->shards[r].device == home ? w->shards[r].q_cnt : (const uint32_t *)w->h_cnt.p + (size_t)slot[r] * n;
+    W_HIP(w, hipSetDevice(home));
+    const size_t nb = (size_t)n / 256 + 2;   // scratch: total | block sums | their scan | summed counts
+    W_HIP(w, dev_grow(w->h_scan, (1 + 2 * nb) * sizeof(unsigned long long) + (size_t)std::max(n, 1u) * sizeof(uint32_t)));
+    unsigned long long *t64 = (unsigned long long *)w->h_scan.p, *bsum = t64 + 1, *boff = bsum + nb;
+    wq_qa_offsets(w->qstream, sh, n, (uint32_t *)(boff + nb), bsum, boff, t64, offsets, total);
+    W_HIP(w, hipGetLastError());
+    W_HIP(w, hipMemcpyAsync(w->q_pin, t64, sizeof(unsigned long long), hipMemcpyDeviceToHost, w->qstream));
+    W_HIP(w, hipStreamSynchronize(w->qstream));
+    *tot = w->q_pin[0];
+    return EDYNHIP_OK;
+}
+
+// The fill pass of the queries counted last: ids [capacity] on the home device; nothing is written at or beyond capacity.
+int world_query_fill(edynhip_world *w, int category, uint32_t n, uint32_t flags, const uint32_t *offsets, uint32_t *ids, uint32_t capacity) {
+    const int home = w->devices[0];
+    std::vector<int32_t> slot;
+    const uint32_t A = active_slots(w, slot);
+    if (n == 0 || A == 0 || capacity == 0) return EDYNHIP_OK;
+    // a shard's own list is sized by its own total: it must be addressable with 32 bits
+    std::vector<size_t> base(w->shards.size(), 0);
+    size_t remote_ids = 0;
+    for (uint32_t r = 0; r < w->shards.size(); ++r) {
+        if (slot[r] < 0) continue;
+        if (*w->shards[r].q_tot >= kSat32) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_query_aabb: a shard reports 2^32 - 1 hits or more");
+        if (w->shards[r].device != home) { base[r] = remote_ids; remote_ids += (size_t)*w->shards[r].q_tot; }
+    }
+    W_HIP(w, hipSetDevice(home));
+    W_HIP(w, dev_grow(w->h_ids, std::max<size_t>(remote_ids, 1) * sizeof(uint32_t)));
+    W_HIP(w, dev_grow(w->h_off, (size_t)A * ((size_t)n + 1) * sizeof(uint32_t)));
+    w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        if (slot[r] < 0 || s.rc != EDYNHIP_OK) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        hipStream_t st = s.ctx->stream;
+        const size_t t = (size_t)*s.q_tot;
+        if (t == 0 && s.device == home) return;
+        SH_HIP(s, dev_grow(s.q_ids, std::max<size_t>(t, 1) * sizeof(uint32_t)));
+        SH_TRY(s, shard_query_fill(s.ctx, category, n, s.q_boxes, flags, (uint32_t *)s.q_ids.p, (uint32_t)t));
+        wq_translate_ids(st, (uint32_t *)s.q_ids.p, t, s.ids_dev, (uint32_t)s.local_ids.size());   // (island labels are body indices too)
+        SH_HIP(s, hipGetLastError());
+        if (s.device != home) {
+            SH_HIP(s, hipMemcpyPeerAsync((uint32_t *)w->h_off.p + (size_t)slot[r] * ((size_t)n + 1), home, s.q_off, s.device, ((size_t)n + 1) * sizeof(uint32_t), st));
+            if (t) SH_HIP(s, hipMemcpyPeerAsync((uint32_t *)w->h_ids.p + base[r], home, s.q_ids.p, s.device, t * sizeof(uint32_t), st));
+        }
+        SH_HIP(s, hipStreamSynchronize(st));
+    });
+    EH_TRY(shard_error(w));
+    WqShards sh{};
+    sh.W = A;
+    for (uint32_t r = 0; r < w->shards.size(); ++r) {
+        if (slot[r] < 0) continue;
+        const Shard &s = w->shards[r];
+        const bool here = s.device == home;
+        sh.off[slot[r]] = here ? s.q_off : (const uint32_t *)w->h_off.p + (size_t)slot[r] * ((size_t)n + 1);
+        sh.ids[slot[r]] = here ? (const uint32_t *)s.q_ids.p : (const uint32_t *)w->h_ids.p + base[r];
+    }
+    W_HIP(w, hipSetDevice(home));
+    for (uint32_t r = 0; r < w->shards.size(); ++r)
+        if (slot[r] >= 0) wq_qa_merge(w->qstream, sh, (uint32_t)slot[r], n, (uint32_t)*w->shards[r].q_tot, offsets, ids, capacity);
+    W_HIP(w, hipGetLastError());
+    W_HIP(w, hipStreamSynchronize(w->qstream));
+    return EDYNHIP_OK;
+}
+
+int check_world_query(edynhip_world *w, int category, uint32_t flags, const char *who) {
+    if (category != EDYNHIP_QUERY_PROCEDURAL && category != EDYNHIP_QUERY_NON_PROCEDURAL && category != EDYNHIP_QUERY_ISLANDS)
+        return w->fail(EDYNHIP_ERR_INVALID, std::string(who) + ": unknown category");
+    if (flags & ~(uint32_t)EDYNHIP_QUERY_BRUTE_FORCE) return w->fail(EDYNHIP_ERR_INVALID, std::string(who) + ": unknown flag bits");
+    return EDYNHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int edynhip_world_raycast_device(edynhip_world *w, uint32_t n, const void *p0_f4, const void *p1_f4, uint32_t num_ignore, const uint32_t *ignore,
+                                 uint32_t flags, void *out) {
+    if (!w || (n && (!p0_f4 || !p1_f4 || !out)) || (num_ignore && !ignore)) return EDYNHIP_ERR_INVALID;
+    if (flags & ~(uint32_t)EDYNHIP_RAYCAST_BRUTE_FORCE) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_raycast_device: unknown flag bits");
+    if (n == 0) return EDYNHIP_OK;
+    EH_TRY(query_begin(w));
+    for (uint32_t off = 0; off < n; off += kWorldChunk)
+        EH_TRY(world_raycast_chunk(w, std::min(kWorldChunk, n - off), (const float4 *)p0_f4 + off, (const float4 *)p1_f4 + off, num_ignore, ignore, flags,
+                                   (edynhip_raycast_hit *)out + off));
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_raycast(edynhip_world *w, uint32_t n, const float *p0, const float *p1, uint32_t num_ignore, const uint32_t *ignore, uint32_t flags,
+                          edynhip_raycast_hit *out) {
+    if (!w || (n && (!p0 || !p1 || !out)) || (num_ignore && !ignore)) return EDYNHIP_ERR_INVALID;
+    if (flags & ~(uint32_t)EDYNHIP_RAYCAST_BRUTE_FORCE) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_raycast: unknown flag bits");
+    if (n == 0) return EDYNHIP_OK;
+    EH_TRY(query_begin(w));
+    const uint32_t chunk = std::min(n, kWorldChunk);
+    W_HIP(w, dev_grow(w->h_in, 2 * (size_t)chunk * sizeof(float4)));
+    W_HIP(w, dev_grow(w->h_out, (size_t)chunk * sizeof(edynhip_raycast_hit)));
+    w->q_stage.resize(2 * (size_t)chunk);
+    for (uint32_t off = 0; off < n; off += kWorldChunk) {
+        const uint32_t m = std::min(kWorldChunk, n - off);
+        for (uint32_t r = 0; r < m; ++r) {
+            const float *q0 = p0 + 3 * ((size_t)off + r), *q1 = p1 + 3 * ((size_t)off + r);
+            w->q_stage[r] = make_float4(q0[0], q0[1], q0[2], 0.0f);
+            w->q_stage[(size_t)chunk + r] = make_float4(q1[0], q1[1], q1[2], 0.0f);
+        }
+        W_HIP(w, hipSetDevice(w->devices[0]));
+        float4 *d = (float4 *)w->h_in.p;
+        W_HIP(w, hipMemcpyAsync(d, w->q_stage.data(), (size_t)m * sizeof(float4), hipMemcpyHostToDevice, w->qstream));
+        W_HIP(w, hipMemcpyAsync(d + chunk, w->q_stage.data() + chunk, (size_t)m * sizeof(float4), hipMemcpyHostToDevice, w->qstream));
+        W_HIP(w, hipStreamSynchronize(w->qstream));
+        EH_TRY(world_raycast_chunk(w, m, d, d + chunk, num_ignore, ignore, flags, w->h_out.p));
+        W_HIP(w, hipMemcpyAsync(out + off, w->h_out.p, (size_t)m * sizeof(edynhip_raycast_hit), hipMemcpyDeviceToHost, w->qstream));
+        W_HIP(w, hipStreamSynchronize(w->qstream));
+    }
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_query_aabb_device(edynhip_world *w, int category, uint32_t n, const void *boxes_f4, uint32_t flags, void *offsets, void *ids,
+                                    uint32_t capacity, void *total) {
+    if (!w || !offsets || !total || (n && !boxes_f4)) return EDYNHIP_ERR_INVALID;
+    EH_TRY(check_world_query(w, category, flags, "edynhip_world_query_aabb_device"));
+    EH_TRY(query_begin(w));
+    unsigned long long tot = 0;
+    EH_TRY(world_query_count(w, category, n, (const float4 *)boxes_f4, flags, (uint32_t *)offsets, (uint32_t *)total, &tot));
+    if (!ids || capacity == 0 || tot == 0) return EDYNHIP_OK;
+    return world_query_fill(w, category, n, flags, (const uint32_t *)offsets, (uint32_t *)ids, capacity);
+}
+
+int edynhip_world_query_aabb(edynhip_world *w, int category, uint32_t n, const float *boxes6, uint32_t flags, uint32_t *offsets, uint32_t *ids,
+                             uint32_t capacity, uint32_t *total) {
+    if (!w || !offsets || !total || (n && !boxes6)) return EDYNHIP_ERR_INVALID;
+    EH_TRY(check_world_query(w, category, flags, "edynhip_world_query_aabb"));
+    EH_TRY(query_begin(w));
+    W_HIP(w, dev_grow(w->h_in, std::max<size_t>(2 * (size_t)n, 1) * sizeof(float4)));
+    W_HIP(w, dev_grow(w->h_off_out, ((size_t)n + 2) * sizeof(uint32_t)));
+    w->q_stage.resize(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *b = boxes6 + 6 * (size_t)i;
+        w->q_stage[2 * (size_t)i] = make_float4(b[0], b[1], b[2], 0.0f);
+        w->q_stage[2 * (size_t)i + 1] = make_float4(b[3], b[4], b[5], 0.0f);
+    }
+    if (n) W_HIP(w, hipMemcpyAsync(w->h_in.p, w->q_stage.data(), 2 * (size_t)n * sizeof(float4), hipMemcpyHostToDevice, w->qstream));
+    W_HIP(w, hipStreamSynchronize(w->qstream));
+    uint32_t *d_off = (uint32_t *)w->h_off_out.p;
+    unsigned long long tot = 0;
+    EH_TRY(world_query_count(w, category, n, (const float4 *)w->h_in.p, flags, d_off, d_off + n + 1, &tot));
+    W_HIP(w, hipMemcpyAsync(offsets, d_off, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, w->qstream));
+    W_HIP(w, hipStreamSynchronize(w->qstream));
+    *total = tot >= kSat32 ? 0xFFFFFFFFu : (uint32_t)tot;
+    if (!ids) return EDYNHIP_OK;
+    if (tot > capacity || tot >= kSat32) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_query_aabb: capacity (offsets and total are valid: size ids by *total and ask again)");
+    if (tot == 0) return EDYNHIP_OK;
+    W_HIP(w, dev_grow(w->h_ids_out, (size_t)tot * sizeof(uint32_t)));
+    EH_TRY(world_query_fill(w, category, n, flags, d_off, (uint32_t *)w->h_ids_out.p, (uint32_t)tot));
+    W_HIP(w, hipMemcpyAsync(ids, w->h_ids_out.p, (size_t)tot * sizeof(uint32_t), hipMemcpyDeviceToHost, w->qstream));
+    W_HIP(w, hipStreamSynchronize(w->qstream));
+    return EDYNHIP_OK;
 }
 
 }  // extern "C"

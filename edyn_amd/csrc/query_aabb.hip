@@ -85,6 +85,7 @@ struct QaArgs {
     uint32_t n_planes, n_bodies;
     const float4 *imin, *imax;        // islands
     const uint32_t *n_islands;
+    const uint32_t *answers;          // a shard of a multi-device world: bit per body it answers for; nullptr: every body
     uint32_t category, mode, scan_ratio;
 };
 
@@ -96,6 +97,7 @@ DI f3 qa_fat_min(float4 a) { return mk3(a.x - kFatInset, a.y - kFatInset, a.z - 
 DI f3 qa_fat_max(float4 a) { return mk3(a.x + kFatInset, a.y + kFatInset, a.z + kFatInset); }
 // procedural: shaped, not removed, dynamic (capi.hip rebuild_broadphase_lists); non-procedural: shaped, not removed, static or kinematic
 DI bool qa_category(const QaArgs &a, uint32_t body) {
+    if (a.answers && !((a.answers[body >> 5] >> (body & 31u)) & 1u)) return false;   // another shard's to answer
     const uint32_t fl = a.flags[body];
     if ((fl & BF_SHAPE_MASK) == 0 || (fl & BF_REMOVED)) return false;
     const bool dyn = (fl & BF_KIND_MASK) == EDYNHIP_KIND_DYNAMIC;
@@ -310,10 +312,11 @@ __global__ void k_qa_isl_clear(uint32_t n, uint32_t *lo, uint32_t *hi, uint32_t 
     if (i < 3 * n) { lo[i] = 0xFFFFFFFFu; hi[i] = 0u; }
     if (i < n) flag[i] = 0u;
 }
-__global__ void k_qa_isl_reduce(uint32_t n, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ island, const float4 *__restrict__ amin,
-                                const float4 *__restrict__ amax, uint32_t *lo, uint32_t *hi, uint32_t *flag) {
+__global__ void k_qa_isl_reduce(uint32_t n, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ island, const uint32_t *__restrict__ answers,
+                                const float4 *__restrict__ amin, const float4 *__restrict__ amax, uint32_t *lo, uint32_t *hi, uint32_t *flag) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (answers && !((answers[i >> 5] >> (i & 31u)) & 1u)) return;
     const uint32_t fl = flags[i];
     if ((fl & BF_KIND_MASK) != EDYNHIP_KIND_DYNAMIC || (fl & BF_REMOVED) || (fl & BF_SHAPE_MASK) == 0) return;
     uint32_t l = island[i];
@@ -382,7 +385,8 @@ static int prepare_islands(edynhip_ctx *c) {
     const uint32_t n = c->b.n;
     if (n) {
         hipLaunchKernelGGL(k_qa_isl_clear, dim3(nblocks(3 * n, 256)), dim3(256), 0, c->stream, n, q.lo, q.hi, q.flag);
-        hipLaunchKernelGGL(k_qa_isl_reduce, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->b.flags, c->b.island, t.amin, t.amax, q.lo, q.hi, q.flag);
+        hipLaunchKernelGGL(k_qa_isl_reduce, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->b.flags,
+                           c->query_island && c->step_index == 0 ? c->query_island : c->b.island, c->answers, t.amin, t.amax, q.lo, q.hi, q.flag);
     }
     EH_TRY(scan_counts(c, q, n, q.flag, q.slot, q.tot + 1, q.ctl + 2, nullptr));
     if (n) hipLaunchKernelGGL(k_qa_isl_compact, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, q.flag, q.slot, q.lo, q.hi, q.imin, q.imax);
@@ -403,7 +407,7 @@ static int run_query(edynhip_ctx *c, int category, uint32_t n, const float4 *box
     QaArgs a;
     a.flags = c->b.flags; a.amin = t.amin; a.amax = t.amax; a.nmin = t.nmin; a.nmax = t.nmax; a.n_tree = t.n_tree;
     a.planes = t.list + t.n_tree; a.n_planes = t.n_planes; a.n_bodies = c->b.n;
-    a.imin = q.imin; a.imax = q.imax; a.n_islands = q.ctl + 2;
+    a.imin = q.imin; a.imax = q.imax; a.n_islands = q.ctl + 2; a.answers = c->answers;
     a.category = (uint32_t)category; a.scan_ratio = q.scan_ratio;
     a.mode = islands ? QA_ISLANDS : (flags & EDYNHIP_QUERY_BRUTE_FORCE) ? QA_BRUTE : QA_TREE;
     const uint32_t want_ids = ids && capacity ? 1u : 0u;
@@ -428,6 +432,32 @@ static int run_query(edynhip_ctx *c, int category, uint32_t n, const float4 *box
     }
     EH_HIP(c, hipGetLastError());
     return EDYNHIP_OK;
+}
+
+// A world's count pass on this shard: counts, offsets and total stay in the context's buffers (the host entry point's), where the world reads them.
+int shard_query_count(edynhip_ctx *c, int category, uint32_t n, const void *boxes_f4, uint32_t flags, const uint32_t **cnt, const uint32_t **offsets,
+                      const unsigned long long **tot64) {
+    EH_HIP(c, hipSetDevice(c->device));
+    EH_TRY(qa_reserve(c, n, false));
+    QueryAabb &q = *c->qa;
+    q.counted = false;
+    if ((size_t)n + 1 > q.off_cap) {
+        EH_HIP(c, hipStreamSynchronize(c->stream));
+        q.off_cap = 0;
+        EH_TRY(qalloc(c, q.d_off, (size_t)n + 1));
+        q.off_cap = (size_t)n + 1;
+    }
+    if (!q.d_total) EH_TRY(qalloc(c, q.d_total, 1));
+    EH_TRY(run_query(c, category, n, (const float4 *)boxes_f4, flags, q.d_off, nullptr, 0, q.d_total, true));
+    c->qa->counted = false;   // (not the host entry point's boxes)
+    *cnt = q.cnt; *offsets = q.d_off; *tot64 = q.tot;
+    return EDYNHIP_OK;
+}
+
+int shard_query_fill(edynhip_ctx *c, int category, uint32_t n, const void *boxes_f4, uint32_t flags, uint32_t *ids, uint32_t capacity) {
+    EH_HIP(c, hipSetDevice(c->device));
+    QueryAabb &q = *c->qa;
+    return run_query(c, category, n, (const float4 *)boxes_f4, flags, q.d_off, ids, capacity, q.d_total, false, true);
 }
 
 }  // namespace eh

@@ -150,6 +150,7 @@ struct RayArgs {
     uint32_t n_planes;
     uint32_t n_bodies;
     const uint32_t *ignore;           // bit per body, or nullptr
+    const uint32_t *answers;          // a shard of a multi-device world: bit per body it answers for; nullptr: every body
     uint32_t brute;
 };
 
@@ -159,6 +160,7 @@ struct Best { dr::RayHit h; uint32_t body; };
 // tie goes to the lower body index).
 DI void rc_candidate(const RayArgs &a, uint32_t body, f3 p0, f3 p1, Best &best) {
     if (a.ignore && ((a.ignore[body >> 5] >> (body & 31u)) & 1u)) return;
+    if (a.answers && !((a.answers[body >> 5] >> (body & 31u)) & 1u)) return;   // another shard's to answer
     const uint32_t fl = a.flags[body];
     const int st = (int)((fl & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT);
     if (st == dc::SHAPE_NONE || (fl & BF_REMOVED)) return;
@@ -234,11 +236,13 @@ static int prepare(edynhip_ctx *c, uint32_t num_ignore, const uint32_t *ignore, 
     const uint32_t n = c->b.n;
     if (t.epoch != c->state_epoch) {
         t.host_list.clear();
+        // (a shard of a multi-device world: the bodies another shard answers for stay out of the tree and of the plane list)
+        auto mine = [&](uint32_t i) { return c->host_answers.empty() || ((c->host_answers[i >> 5] >> (i & 31u)) & 1u); };
         for (uint32_t i = 0; i < n; ++i)
-            if (c->host_shape[i] != EDYNHIP_SHAPE_NONE && c->host_shape[i] != EDYNHIP_SHAPE_PLANE) t.host_list.push_back(i);
+            if (c->host_shape[i] != EDYNHIP_SHAPE_NONE && c->host_shape[i] != EDYNHIP_SHAPE_PLANE && mine(i)) t.host_list.push_back(i);
         t.n_tree = (uint32_t)t.host_list.size();
         for (uint32_t i = 0; i < n; ++i)
-            if (c->host_shape[i] == EDYNHIP_SHAPE_PLANE) t.host_list.push_back(i);
+            if (c->host_shape[i] == EDYNHIP_SHAPE_PLANE && mine(i)) t.host_list.push_back(i);
         t.n_planes = (uint32_t)t.host_list.size() - t.n_tree;
         if (n) hipLaunchKernelGGL(k_rc_boxes, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->b, c->meshes, t.org, t.amin, t.amax);
         if (!t.host_list.empty())   // (pageable source: the copy has read it when the call returns)
@@ -276,6 +280,7 @@ static RayArgs ray_args(edynhip_ctx *c, bool use_mask, uint32_t flags) {
     a.meshes = c->meshes; a.nmin = t.nmin; a.nmax = t.nmax; a.n_tree = t.n_tree;
     a.planes = t.list + t.n_tree; a.n_planes = t.n_planes; a.n_bodies = c->b.n;
     a.ignore = use_mask ? t.mask : nullptr;
+    a.answers = c->answers;
     a.brute = (flags & EDYNHIP_RAYCAST_BRUTE_FORCE) ? 1u : 0u;
     return a;
 }
@@ -286,10 +291,36 @@ static int launch(edynhip_ctx *c, const RayArgs &a, uint32_t n, const float4 *p0
     return EDYNHIP_OK;
 }
 
+static int raycast_device(edynhip_ctx *c, uint32_t n, const void *p0_f4, const void *p1_f4, uint32_t num_ignore, const uint32_t *ignore,
+                          uint32_t flags, void *out) {
+    if (n == 0) return EDYNHIP_OK;
+    EH_HIP(c, hipSetDevice(c->device));
+    bool use_mask = false;
+    EH_TRY(prepare(c, num_ignore, ignore, use_mask));
+    const RayArgs a = ray_args(c, use_mask, flags);
+    const float4 *P0 = (const float4 *)p0_f4, *P1 = (const float4 *)p1_f4;
+    uint4 *O = (uint4 *)out;
+    for (uint32_t off = 0; off < n; off += kChunk)
+        EH_TRY(launch(c, a, std::min(kChunk, n - off), P0 + off, P1 + off, O + 2 * (size_t)off));
+    return EDYNHIP_OK;
+}
+
+void shard_set_answers(edynhip_ctx *c, const uint32_t *answers_dev, std::vector<uint32_t> host_bits, const uint32_t *query_island_dev) {
+    c->answers = answers_dev;
+    c->host_answers = std::move(host_bits);
+    c->query_island = query_island_dev;
+    ++c->state_epoch;   // the query tree and the island boxes hold what the context answered for before
+}
+
+int shard_raycast(edynhip_ctx *c, uint32_t n, const void *p0_f4, const void *p1_f4, uint32_t num_ignore, const uint32_t *ignore, uint32_t flags, void *out) {
+    return raycast_device(c, n, p0_f4, p1_f4, num_ignore, ignore, flags, out);
+}
+
 }  // namespace eh
 
 using namespace eh;
-// Unknown flag bits and shard contexts (edynhip_world_context) are rejected: raycasts on multi-device worlds are not provided.
+// Unknown flag bits and shard contexts (edynhip_world_context) are rejected: a world asks its shards through eh::shard_raycast
+// (edynhip_world_raycast, multi.hip).
 static int check_call(edynhip_ctx *c, uint32_t flags, const char *who) {
     if (flags & ~(uint32_t)EDYNHIP_RAYCAST_BRUTE_FORCE) return set_error(c, EDYNHIP_ERR_INVALID, (std::string(who) + ": unknown flag bits").c_str());
     if (c->world_shard) return set_error(c, EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": a shard of a multi-device world has no raycast").c_str());
@@ -329,14 +360,5 @@ int edynhip_raycast_device(edynhip_ctx *c, uint32_t n, const void *p0_f4, const 
                            uint32_t flags, void *out) {
     if (!c || (n && (!p0_f4 || !p1_f4 || !out)) || (num_ignore && !ignore)) return EDYNHIP_ERR_INVALID;
     EH_TRY(check_call(c, flags, "edynhip_raycast_device"));
-    if (n == 0) return EDYNHIP_OK;
-    EH_HIP(c, hipSetDevice(c->device));
-    bool use_mask = false;
-    EH_TRY(prepare(c, num_ignore, ignore, use_mask));
-    const RayArgs a = ray_args(c, use_mask, flags);
-    const float4 *P0 = (const float4 *)p0_f4, *P1 = (const float4 *)p1_f4;
-    uint4 *O = (uint4 *)out;
-    for (uint32_t off = 0; off < n; off += kChunk)
-        EH_TRY(launch(c, a, std::min(kChunk, n - off), P0 + off, P1 + off, O + 2 * (size_t)off));
-    return EDYNHIP_OK;
+    return raycast_device(c, n, p0_f4, p1_f4, num_ignore, ignore, flags, out);
 }

@@ -108,6 +108,50 @@ class MultiWorld:
         self._check(self._L.edynhip_world_get_manifolds(self._h, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
 
+    # ---- queries: World.raycast / World.query_aabb on the whole world, global body indices (edynhip_world_raycast / _query_aabb)
+    def raycast(self, p0, p1, ignore=(), brute_force=False):
+        """Rays p0[i] -> p1[i] (arrays of shape (n, 3), or one ray of shape (3,)); returns a RAYCAST_HIT_DTYPE array of n records, bit for
+        bit what World.raycast returns on one context holding the whole scene. ignore: global body indices left out."""
+        a = np.ascontiguousarray(np.asarray(p0, np.float32).reshape(-1, 3))
+        b = np.ascontiguousarray(np.asarray(p1, np.float32).reshape(-1, 3))
+        if a.shape != b.shape:
+            raise ValueError("p0 and p1 must hold the same number of points")
+        ign = np.ascontiguousarray(np.asarray(ignore, np.uint32).reshape(-1))
+        out = np.zeros(len(a), _capi.RAYCAST_HIT_DTYPE)
+        flags = _capi.RAYCAST_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_world_raycast(self._h, len(a), _ptr(a), _ptr(b), len(ign), _ptr(ign) if len(ign) else None, flags, _ptr(out)))
+        return out
+
+    def raycast_device(self, n, p0_ptr, p1_ptr, out_ptr, ignore=(), brute_force=False):
+        """Pointers on devices[0]: p0 / p1 hold n float4 (w unused), out receives n 32-byte records. Blocks until the result is complete;
+        the inputs must be complete when it is called."""
+        ign = np.ascontiguousarray(np.asarray(ignore, np.uint32).reshape(-1))
+        flags = _capi.RAYCAST_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_world_raycast_device(self._h, int(n), C.c_void_p(p0_ptr), C.c_void_p(p1_ptr), len(ign),
+                                                         _ptr(ign) if len(ign) else None, flags, C.c_void_p(out_ptr)))
+
+    def query_aabb(self, boxes, category="procedural", brute_force=False):
+        """Boxes (n, 6) = (min, max), or one box of shape (6,). Returns (offsets[n + 1], ids) as World.query_aabb does: global body indices
+        (island labels for "islands") in ascending order per box."""
+        b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 6))
+        cat = _capi.QUERY_CATEGORIES[category] if isinstance(category, str) else int(category)
+        flags = _capi.QUERY_BRUTE_FORCE if brute_force else 0
+        offsets = np.zeros(len(b) + 1, np.uint32)
+        total = C.c_uint32(0)
+        self._check(self._L.edynhip_world_query_aabb(self._h, cat, len(b), _ptr(b), flags, _ptr(offsets), None, 0, C.byref(total)))
+        ids = np.zeros(total.value, np.uint32)
+        if total.value:   # (sized by the count: a second call, which cannot run out of capacity)
+            self._check(self._L.edynhip_world_query_aabb(self._h, cat, len(b), _ptr(b), flags, _ptr(offsets), _ptr(ids), len(ids), C.byref(total)))
+        return offsets, ids
+
+    def query_aabb_device(self, n, boxes_ptr, offsets_ptr, ids_ptr, capacity, total_ptr, category="procedural", brute_force=False):
+        """Pointers on devices[0]: boxes hold 2 n float4 (min, max; w unused), offsets n + 1 uint32, ids `capacity` uint32 (0 / None: count
+        only), total one uint32. Nothing is written at or beyond `capacity`. Blocks until the result is complete."""
+        cat = _capi.QUERY_CATEGORIES[category] if isinstance(category, str) else int(category)
+        flags = _capi.QUERY_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_world_query_aabb_device(self._h, cat, int(n), C.c_void_p(boxes_ptr), flags, C.c_void_p(offsets_ptr),
+                                                            C.c_void_p(ids_ptr) if ids_ptr else None, int(capacity), C.c_void_p(total_ptr)))
+
     def get_stats(self):
         st = _capi.WorldStats()
         self._check(self._L.edynhip_world_get_stats(self._h, C.byref(st)))

@@ -587,6 +587,28 @@ int edynhip_world_get_manifolds(edynhip_world *w, edynhip_manifold *out, uint32_
 int edynhip_world_get_stats(edynhip_world *w, edynhip_world_stats *out);
 edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard);        /* a shard's context (read-only use: statistics, timings) */
 
+/* edynhip_raycast / edynhip_query_aabb on a multi-device world (additive to ABI 15). Arguments, result layout, flags, capacity rules and
+ * error codes are those of the single-context calls; every body index - the ignore list, hit.body, ids, island labels - is GLOBAL. The
+ * answer is bit for bit what ONE context holding the whole scene returns for the same call: every body is answered by exactly one
+ * shard (shard 0: the replicated non-dynamic bodies and its own dynamic ones; any other shard: the dynamic bodies it owns) with the
+ * single context's kernels, local indices are translated on the shard's device, and the answers are merged on the home device,
+ * devices[0] (smallest fraction, ties to the lowest global index; hit lists in ascending global index) - edyn_amd/csrc/world_query.hip.
+ * A world that has been described but not stepped builds its shards first, as edynhip_world_step does, and is seen in the described
+ * state; after a step the queries see the state edynhip_world_get_state returns. A query changes nothing a later step computes.
+ * The public single-context calls keep refusing a shard context (edynhip_world_context) with EDYNHIP_ERR_UNSUPPORTED.
+ * The _device variants take pointers on devices[0]. Unlike the single-context ones they BLOCK the calling thread until every shard has
+ * answered and the merge has run: the inputs must be complete when the call is made (synchronise the stream that wrote them) and the
+ * results are complete when it returns. Rays, boxes, hits and ids travel device to device, never through pageable host memory.
+ * edynhip_world_query_aabb_device with ids: every shard's own total must be below 2^32 - 1 (EDYNHIP_ERR_CAPACITY otherwise). */
+int edynhip_world_raycast(edynhip_world *w, uint32_t n, const float *p0, const float *p1,
+                          uint32_t num_ignore, const uint32_t *ignore, uint32_t flags, edynhip_raycast_hit *out);
+int edynhip_world_raycast_device(edynhip_world *w, uint32_t n, const void *p0_f4, const void *p1_f4,
+                          uint32_t num_ignore, const uint32_t *ignore, uint32_t flags, void *out);
+int edynhip_world_query_aabb(edynhip_world *w, int category, uint32_t n, const float *boxes6, uint32_t flags,
+                          uint32_t *offsets, uint32_t *ids, uint32_t capacity, uint32_t *total);
+int edynhip_world_query_aabb_device(edynhip_world *w, int category, uint32_t n, const void *boxes_f4, uint32_t flags,
+                          void *offsets, void *ids, uint32_t capacity, void *total);
+
 /* The pieces of the above that processes owning ONE GPU each use (edyn_amd/parallel.py ShardedWorld over torch.distributed / RCCL):
  * the island partitioner - longest-processing-time-first over the summed weights, deterministic (islands by descending weight, ties
  * by ascending label, each to the lightest rank, ties to the lowest rank); rank_of[i] = -1 for non-dynamic bodies. weights may be
