@@ -559,6 +559,7 @@ edynhip_ctx *edynhip_create(const edynhip_config *cfg, int *status_out) {
     edynhip_ctx *c = new edynhip_ctx();
     c->cfg = *cfg;
     c->sleeping = (cfg->flags & EDYNHIP_FLAG_SLEEPING) != 0;
+    c->np_fused = !(getenv("EDYNHIP_NP_FUSED") && getenv("EDYNHIP_NP_FUSED")[0] == '0');   // developer knob (A/B): 0 = k_np_detect + k_np_merge through the staging arrays
     c->device = cfg->device;
     if (c->cfg.max_manifolds == 0) c->cfg.max_manifolds = 16 * c->cfg.max_bodies + 1024;
     if (c->cfg.fixed_dt <= 0) c->cfg.fixed_dt = 1.0f / 60.0f;

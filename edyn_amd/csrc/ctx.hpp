@@ -366,6 +366,7 @@ struct edynhip_ctx {
     bool all_asleep = false;       // the last step left every procedural body asleep and nothing was edited since: steps are no-ops
     bool solve_begin_done = false; // this step's k_cc_flatten already did k_solve_begin's work (solver.hip islands())
     bool has_generic = false;      // some joint is a generic_constraint (k_prep_generic runs)
+    bool np_fused = true;          // narrowphase.hip: k_np_contacts (detect + merge in one pass) for the pairs collide() serves; EDYNHIP_NP_FUSED=0 at creation turns it off
     bool has_cylinder = false;     // some body is a cylinder_shape (narrowphase.hip k_np_detect_ext runs)
     // convex meshes and polyhedron bodies (mesh.hip)
     bool has_polyhedron = false;   // some body is a polyhedron_shape (k_update_rotated + k_np_detect_poly run)

@@ -55,9 +55,11 @@ DI bool should_remove(const CPoint &cp, const BodyIn &A, const BodyIn &B) {
     return nd > thr || length_sqr(td) > thr2;
 }
 
-// Two kernels, so that neither has to hold the closest-feature search and the manifold bookkeeping in registers at once:
+// The staged path - two kernels, so that neither has to hold the closest-feature search and the manifold bookkeeping in registers at once:
 //   k_np_detect  detect_collision: AABB pre-check + collide() -> the raw result (<= 4 points) into a staging array
 //   k_np_merge   update_contact_distances + process_collision: old points x result -> the manifold's new point list
+// Box, sphere, plane and capsule pairs go through k_np_contacts (below) in one pass by default; k_np_detect remains for EDYNHIP_NP_FUSED=0,
+// the staging arrays for that and for the cylinder / polyhedron kernels.
 // Staging layout per result point slot k of manifold m, at [k * cap + m]: ra = (pivotA, distance), rb = (pivotB, bits(attachment)),
 // rn = (normal, -); rnum[m] = number of result points.
 struct Staging { float4 *ra, *rb, *rn; uint32_t *rnum; };
@@ -299,10 +301,31 @@ k_np_pp_contacts(Manifolds mf, Bodies b, Staging st, Meshes meshes, PolyBins pb,
     }
 }
 
-__global__ void __launch_bounds__(64, 2)
-k_np_merge(uint32_t M, Manifolds mf, Bodies b, float dt, bool sleeping, Manifolds old, bool points_in_old, Staging st, EventSink ev) {
-    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m < M) {
+// Where np_merge_lane reads a manifold's raw collide() result from: the staging arrays (k_np_merge) or the wave's LDS block (k_np_contacts).
+struct StagedResult {
+    Staging st; size_t cap; uint32_t m;
+    DI int num() const { return (int)st.rnum[m]; }
+    DI CPoint point(int k) const {
+        const size_t d = (size_t)k * cap + m;
+        const float4 ra = st.ra[d], rb = st.rb[d], rn = st.rn[d];
+        return CPoint{from4(ra), from4(rb), from4(rn), ra.w, __float_as_int(rb.w)};
+    }
+};
+// Lane-minor: the float4 q of lane l sits at [q * 64 + l] and its count at [l], so that a wave's accesses are contiguous (no bank conflicts).
+constexpr int kNpLdsQuads = 3 * kMaxPts;
+struct LdsResult {
+    const float4 *q; const int *n;   // this lane's column of the wave's block, its count
+    DI int num() const { return *n; }
+    DI CPoint point(int k) const {
+        const float4 ra = q[(3 * k) * 64], rb = q[(3 * k + 1) * 64], rn = q[(3 * k + 2) * 64];
+        return CPoint{from4(ra), from4(rb), from4(rn), ra.w, __float_as_int(rb.w)};
+    }
+};
+
+// update_contact_distances + process_collision of manifold m: old points x raw result -> the manifold's new point list.
+template <class Result>
+DI void np_merge_lane(const uint32_t m, const Manifolds &mf, const Bodies &b, float dt, bool sleeping, const Manifolds &old, bool points_in_old, const Result &raw, const EventSink &ev) {
+    {
         const uint32_t ia = mf.bodyA[m], ib = mf.bodyB[m];
         const uint32_t info = mf.info[m];
         const int n_old = (int)(info & 0xFF);
@@ -347,17 +370,12 @@ k_np_merge(uint32_t M, Manifolds mf, Bodies b, float dt, bool sleeping, Manifold
             }
         }
 
-        const int R = (int)st.rnum[m];
+        const int R = raw.num();
         CPoint rs[kMaxPts];
 #pragma unroll
         for (int k = 0; k < kMaxPts; ++k) {
-            if (k < R) {
-                const size_t d = (size_t)k * mf.cap + m;
-                const float4 ra = st.ra[d], rb = st.rb[d], rn = st.rn[d];
-                rs[k] = CPoint{from4(ra), from4(rb), from4(rn), ra.w, __float_as_int(rb.w)};
-            } else {
-                rs[k] = CPoint{};
-            }
+            if (k < R) rs[k] = raw.point(k);
+            else rs[k] = CPoint{};
         }
 
         // ---- process_collision ----
@@ -522,6 +540,69 @@ k_np_merge(uint32_t M, Manifolds mf, Bodies b, float dt, bool sleeping, Manifold
     }
 }
 
+// Manifolds that the staged kernels serve (k_np_detect_ext, k_np_detect_poly, k_np_pp_*): a cylinder or a polyhedron on either side.
+DI bool np_staged_pair(uint32_t fa, uint32_t fb) {
+    const int tA = (int)((fa & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT), tB = (int)((fb & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT);
+    return tA == SHAPE_CYLINDER || tB == SHAPE_CYLINDER || tA == SHAPE_POLYHEDRON || tB == SHAPE_POLYHEDRON;
+}
+
+// staged_only: k_np_contacts served the other manifolds (box, sphere, plane, capsule pairs) already
+__global__ void __launch_bounds__(64, 2)
+k_np_merge(uint32_t M, Manifolds mf, Bodies b, float dt, bool sleeping, Manifolds old, bool points_in_old, Staging st, EventSink ev, bool staged_only) {
+    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    if (staged_only && !np_staged_pair(b.flags[mf.bodyA[m]], b.flags[mf.bodyB[m]])) return;
+    np_merge_lane(m, mf, b, dt, sleeping, old, points_in_old, StagedResult{st, mf.cap, m}, ev);
+}
+
+// k_np_detect and k_np_merge in one pass for the pairs that collide() serves (box, sphere, plane, capsule): the closest-feature search
+// and the manifold bookkeeping do not fit in 256 registers together (why there were two kernels), but nothing of the search has to
+// outlive it except the raw result - so the lane parks that in LDS (12.25 KiB per wave, lane-minor) and reads it back once the search's
+// registers are dead. The fence between the phases keeps the compiler from forwarding the stores to the loads, which would stretch
+// the search's live ranges across the merge again. The staging arrays' write and read-back (HBM) go, and one launch.
+// staged_world: the world has a cylinder or a polyhedron - such pairs get rnum = 0 here (the staged detect kernels rely on it, as they
+// did on k_np_detect) and are merged by k_np_merge(staged_only).
+__global__ void __launch_bounds__(64, 2)
+k_np_contacts(uint32_t M, Manifolds mf, Bodies b, float dt, bool sleeping, Manifolds old, bool points_in_old, uint32_t *rnum, EventSink ev, bool staged_world) {
+    __shared__ float4 park[kNpLdsQuads * 64];
+    __shared__ int park_num[64];   // -1: not this kernel's manifold
+    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+    float4 *const mine = park + threadIdx.x;
+    int num = -1;
+    // ---- phase A: detect_collision (k_np_detect) ----
+    if (m < M) {
+        const uint32_t ia = mf.bodyA[m], ib = mf.bodyB[m];
+        const uint32_t fa = b.flags[ia], fb = b.flags[ib];
+        if (staged_world && np_staged_pair(fa, fb)) {
+            rnum[m] = 0;
+        } else {
+            num = 0;
+            if (!(sleeping && edge_asleep(fa, fb))) {
+                const box3 ba{from4(b.amin[ia]), from4(b.amax[ia])}, bbx{from4(b.amin[ib]), from4(b.amax[ib])};
+                if (intersect(inset(ba, -kBreakingThreshold), bbx)) {
+                    const int tA = (int)((fa & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT), tB = (int)((fb & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT);
+                    Ctx ctx{B_ORG(b, ia), q_from4(B_ORN(b, ia)), B_ORG(b, ib), q_from4(B_ORN(b, ib)), kCollisionThreshold};   // shapes sit at the origin (collision_util.cpp:451-465)
+                    CResult res;
+                    res.num = 0;
+                    collide(tA, b.shape[ia], tB, b.shape[ib], ctx, res);
+                    num = res.num;
+#pragma unroll
+                    for (int k = 0; k < kMaxPts; ++k) {
+                        if (k >= res.num) break;
+                        mine[(3 * k) * 64] = to4(res.pt[k].pivotA, res.pt[k].distance);
+                        mine[(3 * k + 1) * 64] = to4(res.pt[k].pivotB, __int_as_float(res.pt[k].attachment));
+                        mine[(3 * k + 2) * 64] = to4(res.pt[k].normal, 0.0f);
+                    }
+                }
+            }
+        }
+    }
+    park_num[threadIdx.x] = num;
+    __syncthreads();   // one wave per workgroup: a fence for the compiler and the LDS counter, every lane reads its own column
+    // ---- phase B: update_contact_distances + process_collision (k_np_merge) ----
+    if (park_num[threadIdx.x] >= 0) np_merge_lane(m, mf, b, dt, sleeping, old, points_in_old, LdsResult{mine, &park_num[threadIdx.x]}, ev);
+}
+
 // Contact point / active manifold census for edynhip_get_stats (not on the per-step path).
 __global__ void k_count_points(uint32_t M, const uint32_t *__restrict__ info, Counters *cnt) {
     uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -659,7 +740,12 @@ int narrowphase(edynhip_ctx *c) {
     const uint32_t M = c->num_manifolds;
     if (M == 0) return EDYNHIP_OK;
     const Staging st{c->np_ra, c->np_rb, c->np_rn, c->np_rnum};
-    hipLaunchKernelGGL(k_np_detect, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->sleeping, st);
+    const bool staged_world = c->has_cylinder || c->has_polyhedron;
+    if (c->np_fused)
+        hipLaunchKernelGGL(k_np_contacts, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->cfg.fixed_dt, c->sleeping, c->m[c->cur ^ 1], c->points_in_prev, c->np_rnum,
+                           event_sink(c), staged_world);
+    else
+        hipLaunchKernelGGL(k_np_detect, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->sleeping, st);
     if (c->has_cylinder) hipLaunchKernelGGL(k_np_detect_ext, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->sleeping, st);
     if (c->has_polyhedron) {
         EH_TRY(update_rotated(c));
@@ -708,7 +794,9 @@ int narrowphase(edynhip_ctx *c) {
         }
         hipLaunchKernelGGL(k_np_detect_poly, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, st, c->meshes, pb, group != 0);
     }
-    hipLaunchKernelGGL(k_np_merge, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->cfg.fixed_dt, c->sleeping, c->m[c->cur ^ 1], c->points_in_prev, st, event_sink(c));
+    if (!c->np_fused || staged_world)
+        hipLaunchKernelGGL(k_np_merge, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->cfg.fixed_dt, c->sleeping, c->m[c->cur ^ 1], c->points_in_prev, st, event_sink(c),
+                           c->np_fused);
     c->points_in_prev = false;
     EH_HIP(c, hipGetLastError());
     return EDYNHIP_OK;
