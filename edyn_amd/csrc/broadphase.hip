@@ -666,10 +666,6 @@ __global__ void k_bp_build_manifolds(const uint64_t *__restrict__ skeys, uint32_
 }
 
 static inline uint32_t blocks(uint32_t n, uint32_t bs) { return (n + bs - 1) / bs; }
-static bool bp_lists_enabled() {   // development knob: EDYNHIP_BP_LISTS=0 walks the tree every step
-    static const bool on = !(getenv("EDYNHIP_BP_LISTS") && getenv("EDYNHIP_BP_LISTS")[0] == '0');
-    return on;
-}
 
 // Contact events: the previous step's manifolds that no pair of this step continues (destroy_separated_manifolds,
 // broadphase.cpp:99-134; or a body was removed) - their points end with them.
@@ -734,14 +730,14 @@ int broadphase(edynhip_ctx *c) {
         // whose list overflowed walks the tree in k_bp_pairs EVERY step - with last refit's records under this step's leaf order it
         // would test the wrong bodies (found by the settled C3 scene: fast spheres, lists of > 64 candidates, pairs lost in the step
         // after a topology rebuild). So a rebuild step refits and re-walks.
-        const uint32_t force = (c->bvh.lists_dirty || !c->full_step || !bp_lists_enabled() || rebuild) ? 1u : 0u;
+        const uint32_t force = (c->bvh.lists_dirty || !c->full_step || !c->knobs.bp_lists || rebuild) ? 1u : 0u;
         c->bvh.lists_dirty = false;
         hipLaunchKernelGGL(k_bp_refit, dim3(blocks(np, 256)), dim3(256), 0, s, c->bvh.keys_sorted, (int)np, c->bvh.parent, c->bvh.left, c->bvh.right, c->bvh.rope, c->b.amin, c->b.amax, c->bvh.nmin, c->bvh.nmax, c->bvh.visit, c->cnt, c->bvh.ref_min, c->bvh.ref_max, c->b.linvel, c->b.angvel, c->cfg.fixed_dt, force,
                            sqrtf(c->cfg.gravity[0] * c->cfg.gravity[0] + c->cfg.gravity[1] * c->cfg.gravity[1] + c->cfg.gravity[2] * c->cfg.gravity[2]), c->bvh.lookahead);
         hipLaunchKernelGGL(k_bp_walk, dim3(blocks(np * kWalkLanes, 256)), dim3(256), 0, s, c->bvh.keys_sorted, (int)np, c->bvh.nmin, c->bvh.nmax, c->b.amin, c->b.amax, cl, c->cnt, c->bvh.visit, c->sleeping, force, c->bvh.right);
         hipLaunchKernelGGL(k_bp_pairs, dim3(blocks(np, kOwnersPerBlock)), dim3(kBpBlock), 0, s, c->bvh.keys_sorted, (int)np, c->bvh.nmin, c->bvh.nmax, c->b.amin, c->b.amax, Filt{c->b.group, c->b.mask, c->excl, c->pair_filter != nullptr}, c->bvh.np_list, c->bvh.num_np, prev, pm, c->own_keys, c->own_count, c->pair_keys, cur.cap, c->cnt, cl, c->b.flags, c->sleeping, c->bvh.split, c->bvh.rope);
         {   // developer knob EDYNHIP_BP_STATS=1: what k_bp_pairs had to do, every 100th step (candidate-list lengths, owners that walked the tree, pairs kept)
-            static const bool bp_stats = getenv("EDYNHIP_BP_STATS") != nullptr;
+            const bool bp_stats = c->knobs.bp_stats;
             if (bp_stats && c->step_index % 100 == 50) {
                 std::vector<uint32_t> cnt(c->b.n), own(c->b.n);
                 EH_HIP(c, hipMemcpyAsync(cnt.data(), c->bvh.cand_count, (size_t)c->b.n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -762,7 +758,7 @@ int broadphase(edynhip_ctx *c) {
             }
         }
         // owners in index order: offsets = exclusive scan of the per-owner counts (own_count[n] = 0 -> own_offset[n] = total)
-        static const bool direct_env = !(getenv("EDYNHIP_DIRECT_COMPACT") && getenv("EDYNHIP_DIRECT_COMPACT")[0] == '0');   // developer knob (A/B)
+        const bool direct_env = c->knobs.direct_compact;   // developer knob (A/B)
         if (c->b.n <= kCompactScanBodies && direct_env) {
             hipLaunchKernelGGL(k_bp_compact<true>, dim3(blocks(c->b.n, 256)), dim3(256), 0, s, c->b.n, c->own_keys, c->own_count, c->own_offset, c->pair_keys, c->pair_keys_sorted, cur.cap, c->cnt, prev.skey, pm);
         } else {
@@ -773,8 +769,8 @@ int broadphase(edynhip_ctx *c) {
         // step the build is enqueued right behind the counter publish, over a grid sized from last step's count, reads the count on the
         // device and stands down by itself in the cases decided below (speculative launch; what its grid did not cover is launched
         // after the fetch). The GPU builds while the answer travels to the host (11 us of idle GPU per step on the headline pile).
-        static const bool spec_env = !(getenv("EDYNHIP_SPECULATE") && getenv("EDYNHIP_SPECULATE")[0] == '0');
-        static const bool inplace_env = !(getenv("EDYNHIP_INPLACE") && getenv("EDYNHIP_INPLACE")[0] == '0');
+        const bool spec_env = c->knobs.speculate;
+        const bool inplace_env = c->knobs.inplace;
         const bool inplace_allowed = inplace_env && c->full_step && !c->events && !c->force_islands;
         const EventSink ev = event_sink(c);
         uint32_t covered = 0;
@@ -791,7 +787,7 @@ int broadphase(edynhip_ctx *c) {
         if (c->cnt_host->df_abort) return set_error(c, EDYNHIP_ERR_INTERNAL, "dataflow solve: a hand-off never arrived in the previous step (workgroups not co-resident?)");
         M = c->cnt_host->num_pairs;
         {   // adapt the lists' look-ahead (ctx.hpp LBVH::lookahead): rebuilt in each of the last 4 steps -> halve; at most twice in the last 8 -> double
-            static const bool adapt = !(getenv("EDYNHIP_BP_ADAPT") && getenv("EDYNHIP_BP_ADAPT")[0] == '0');   // developer knob (A/B)
+            const bool adapt = c->knobs.bp_adapt;   // developer knob (A/B)
             const bool rebuilt = force != 0 || c->cnt_host->bp_rebuilt != 0;
             c->bvh.rebuild_hist = (c->bvh.rebuild_hist << 1) | (rebuilt ? 1u : 0u);
             if (adapt && c->full_step) {

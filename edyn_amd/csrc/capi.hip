@@ -1,6 +1,6 @@
 // C-ABI implementation (include/edynhip.h): context lifetime, scene upload, step orchestration,
 // state read-back. Host-side logic only; every simulation stage runs in the HIP kernels of
-// broadphase.hip / narrowphase.hip / solver.hip. There is no CPU fallback.
+// broadphase.hip / narrowphase.hip / islands.hip / colouring.hip / solver.hip. There is no CPU fallback.
 #include "ctx.hpp"
 #include "dpolyhedron.hpp"
 #include <algorithm>
@@ -19,6 +19,66 @@ int set_error(edynhip_ctx *c, int code, const char *what, hipError_t e) {
     if (e != hipSuccess) { msg += ": "; msg += hipGetErrorString(e); }
     if (c) c->err = msg; else g_create_error = msg;
     return code;
+}
+
+// The development knobs (ctx.hpp Knobs). One row per variable: its name, its kind, its default, the field it fills and one line of
+// meaning. ON: on unless the value starts with '0'. OFF: off unless the value starts with '1'. SET: off unless the variable is set, to
+// whatever value. NUM: a number. PATH: a file name. The default column is the value of an unset variable (PATH: none).
+// scripts/README.md carries the same rows (tests/test_knobs.py compares the two lists).
+namespace {
+enum KnobKind { KNOB_ON, KNOB_OFF, KNOB_SET, KNOB_NUM, KNOB_PATH };
+struct KnobRow {
+    const char *name; KnobKind kind; long def;
+    bool Knobs::*flag; long Knobs::*num; std::string Knobs::*path;
+    const char *meaning;
+};
+constexpr KnobRow kKnobTable[] = {
+    {"EDYNHIP_DATAFLOW", KNOB_ON, 1, &Knobs::dataflow, nullptr, nullptr, "0: no dataflow launches, the per-colour schedule"},
+    {"EDYNHIP_DATAFLOW_POS", KNOB_ON, 1, &Knobs::dataflow_pos, nullptr, nullptr, "0: the position solve per colour"},
+    {"EDYNHIP_DF_LANES", KNOB_NUM, 0, nullptr, &Knobs::df_lanes, nullptr, "1, 2 or 4: lanes per manifold of the dataflow velocity kernel (0: chosen per step)"},
+    {"EDYNHIP_DF_WAVES", KNOB_NUM, 0, nullptr, &Knobs::df_waves, nullptr, "resident waves of the dataflow velocity kernel (0: chosen per step)"},
+    {"EDYNHIP_DFP_WAVES", KNOB_NUM, 0, nullptr, &Knobs::dfp_waves, nullptr, "resident waves of the dataflow position kernel (0: chosen per step)"},
+    {"EDYNHIP_DF_NAP", KNOB_NUM, 1, nullptr, &Knobs::df_nap, nullptr, "pause between two polls of a wave that found nothing in the dataflow velocity kernels: 0 none, 1 short, else longer"},
+    {"EDYNHIP_DF_XCD", KNOB_OFF, 0, &Knobs::df_xcd, nullptr, nullptr, "1: XCD-local task lists in the two-lane velocity kernel and the position kernel"},
+    {"EDYNHIP_DF_TRACE", KNOB_PATH, 0, nullptr, nullptr, &Knobs::df_trace, "file that receives four timestamps per task of one dataflow velocity solve (scripts/df_trace.py)"},
+    {"EDYNHIP_DFP_TRACE", KNOB_PATH, 0, nullptr, nullptr, &Knobs::dfp_trace, "the same for one dataflow position solve"},
+    {"EDYNHIP_DF_TRACE_STEP", KNOB_NUM, 100, nullptr, &Knobs::df_trace_step, nullptr, "which of the context's dataflow solves the two traces record"},
+    {"EDYNHIP_ISLAND_FUSED", KNOB_ON, 1, &Knobs::island_fused, nullptr, nullptr, "0: no island-fused schedule"},
+    {"EDYNHIP_MIXED", KNOB_ON, 1, &Knobs::mixed, nullptr, nullptr, "0: no mixed schedule"},
+    {"EDYNHIP_SPECULATE", KNOB_ON, 1, &Knobs::speculate, nullptr, nullptr, "0: wait for the counters before the manifold build and the row preparation"},
+    {"EDYNHIP_INPLACE", KNOB_ON, 1, &Knobs::inplace, nullptr, nullptr, "0: rebuild the manifold array every step"},
+    {"EDYNHIP_BP_LISTS", KNOB_ON, 1, &Knobs::bp_lists, nullptr, nullptr, "0: walk the tree every step instead of keeping candidate lists"},
+    {"EDYNHIP_BP_ADAPT", KNOB_ON, 1, &Knobs::bp_adapt, nullptr, nullptr, "0: the candidate lists' look-ahead stays fixed"},
+    {"EDYNHIP_BP_STATS", KNOB_SET, 0, &Knobs::bp_stats, nullptr, nullptr, "set: what k_bp_pairs had to do, on stderr every 100 steps"},
+    {"EDYNHIP_DIRECT_COMPACT", KNOB_ON, 1, &Knobs::direct_compact, nullptr, nullptr, "0: the library-scan form of the pair compaction"},
+    {"EDYNHIP_DIRECT_SORT", KNOB_ON, 1, &Knobs::direct_sort, nullptr, nullptr, "0: the library-scan form of the colour sort"},
+    {"EDYNHIP_COL_LDS", KNOB_OFF, 0, &Knobs::col_lds, nullptr, nullptr, "1: the one-workgroup colouring rounds keep their marks in a hashed LDS table (k_col_rounds_lds)"},
+    {"EDYNHIP_CC_COMPRESS", KNOB_NUM, 1, nullptr, &Knobs::cc_compress, nullptr, "pointer-jumping passes of a full island relabel"},
+    {"EDYNHIP_TREE_STATS", KNOB_SET, 0, &Knobs::tree_stats, nullptr, nullptr, "set: on destruction, how many steps relabelled the islands in full and incrementally"},
+    {"EDYNHIP_NP_FUSED", KNOB_ON, 1, &Knobs::np_fused, nullptr, nullptr, "0: k_np_detect + k_np_merge through the staging arrays instead of k_np_contacts"},
+    {"EDYNHIP_POLY_GROUP", KNOB_NUM, 8, nullptr, &Knobs::poly_group, nullptr, "polyhedron pairs: 0 = one lane per pair in k_np_detect_poly, 8 or 16 = lanes per pair in k_np_pp_axes"},
+    {"EDYNHIP_POLY_GROUP2", KNOB_NUM, 4, nullptr, &Knobs::poly_group2, nullptr, "4, 8 or 16: lanes per surviving pair in k_np_pp_contacts"},
+    {"EDYNHIP_POLY_HINT", KNOB_ON, 1, &Knobs::poly_hint, nullptr, nullptr, "0: no separating-axis hints"},
+    {"EDYNHIP_PP_PROF", KNOB_SET, 0, &Knobs::pp_prof, nullptr, nullptr, "set: phase profile of the two polyhedron-pair kernels, on stderr every 100 steps"},
+    {"EDYNHIP_QUERY_SCAN_RATIO", KNOB_NUM, 0, nullptr, &Knobs::query_scan_ratio, nullptr, "AABB queries: a query with more than bodies / ratio hits is packed by a wave (0: the built-in ratio)"},
+    {"EDYNHIP_RECORDS_DIRECT", KNOB_NUM, -1, nullptr, &Knobs::records_direct, nullptr, "0 or 1: overrides EDYNHIP_SNAPSHOT_DIRECT of edynhip_snapshot_records (-1: the caller's flag)"},
+    {"EDYNHIP_WORLD_SERIAL", KNOB_SET, 0, &Knobs::world_serial, nullptr, nullptr, "set: a multi-device world runs every shard on the caller's thread"},
+    {"EDYNHIP_WORLD_TRACE", KNOB_SET, 0, &Knobs::world_trace, nullptr, nullptr, "set: wall time of the phases of a re-partition, on stderr"},
+};
+}  // namespace
+Knobs read_knobs() {
+    Knobs k{};
+    for (const KnobRow &r : kKnobTable) {
+        const char *e = getenv(r.name);
+        switch (r.kind) {
+        case KNOB_ON: k.*r.flag = e ? e[0] != '0' : r.def != 0; break;
+        case KNOB_OFF: k.*r.flag = e ? e[0] == '1' : r.def != 0; break;
+        case KNOB_SET: k.*r.flag = e != nullptr; break;
+        case KNOB_NUM: k.*r.num = e ? atol(e) : r.def; break;
+        case KNOB_PATH: k.*r.path = e ? e : ""; break;
+        }
+    }
+    return k;
 }
 
 // Host <- device counters without a stream synchronisation: a one-workgroup kernel copies the counter block into pinned
@@ -559,7 +619,7 @@ edynhip_ctx *edynhip_create(const edynhip_config *cfg, int *status_out) {
     edynhip_ctx *c = new edynhip_ctx();
     c->cfg = *cfg;
     c->sleeping = (cfg->flags & EDYNHIP_FLAG_SLEEPING) != 0;
-    c->np_fused = !(getenv("EDYNHIP_NP_FUSED") && getenv("EDYNHIP_NP_FUSED")[0] == '0');   // developer knob (A/B): 0 = k_np_detect + k_np_merge through the staging arrays
+    c->knobs = read_knobs();
     c->device = cfg->device;
     if (c->cfg.max_manifolds == 0) c->cfg.max_manifolds = 16 * c->cfg.max_bodies + 1024;
     if (c->cfg.fixed_dt <= 0) c->cfg.fixed_dt = 1.0f / 60.0f;
@@ -578,7 +638,7 @@ edynhip_ctx *edynhip_create(const edynhip_config *cfg, int *status_out) {
 
 void edynhip_destroy(edynhip_ctx *c) {
     if (!c) return;
-    if (getenv("EDYNHIP_TREE_STATS"))   // developer knob: how the island labels were kept up to date (solver.hip islands)
+    if (c->knobs.tree_stats)   // developer knob: how the island labels were kept up to date (islands.hip islands)
         fprintf(stderr, "[edynhip] island labels: %llu steps relabelled in full, %llu incrementally\n", (unsigned long long)c->cc_full_steps, (unsigned long long)c->cc_incremental_steps);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -738,7 +798,7 @@ int edynhip_add_bodies(edynhip_ctx *c, uint32_t n, const edynhip_bodies *in) {
 }
 
 // Host joint list -> device arrays: deterministic edge colouring over the live joints in caller-index order (the rule of the
-// per-step contact colouring, solver.hip k_col_*), colour-sorted upload, applied impulses and hinge angles carried along.
+// per-step contact colouring, colouring.hip k_col_*), colour-sorted upload, applied impulses and hinge angles carried along.
 // fetch = first read the current impulses / angles back from the device (the joints were stepped since the last rebuild).
 static int rebuild_joints(edynhip_ctx *c, bool fetch) {
     Joints &j = c->j;
@@ -1724,10 +1784,10 @@ int edynhip_snapshot_records(edynhip_ctx *c, float present_dt, uint32_t max_even
     const size_t ev_bytes = (size_t)c->rec_event_cap * sizeof(eh::ContactEvent);
     uint8_t *d = c->rec_dev[slot], *h = c->rec_host[slot];
     // EDYNHIP_SNAPSHOT_DIRECT: the pack kernels store straight into the pinned host slot (it is mapped into the device's address space) on the
-    // stepper's stream - no copy engine, no second stream, no event between the two. A/B on one box (scripts/runs/r6l.sh): edyn::update in
+    // stepper's stream - no copy engine, no second stream, no event between the two. A/B on one box ("Round 6"): edyn::update in
     // sequential mode 705 -> 727 steps/s; in asynchronous mode, where nobody waits for the snapshot, the copy engine's overlap is worth as much
     // (785 / 759 against 764 / 765): the shim asks for it in its synchronous write-back only. (developer knob EDYNHIP_RECORDS_DIRECT=0 / 1 overrides)
-    static const int direct_env = getenv("EDYNHIP_RECORDS_DIRECT") ? atoi(getenv("EDYNHIP_RECORDS_DIRECT")) : -1;
+    const long direct_env = c->knobs.records_direct;
     const bool direct = direct_env >= 0 ? direct_env != 0 : (flags & EDYNHIP_SNAPSHOT_DIRECT) != 0;
     if (direct) {
         if (n) hipLaunchKernelGGL(k_pack_records, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->b, present_dt, (float4 *)(h + kRecHeader + ev_bytes));

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <array>
 #include <map>
@@ -27,7 +28,7 @@ constexpr int kMaxPts = 4;
 constexpr uint32_t BF_KIND_MASK = 0x3u;        // EDYNHIP_KIND_*
 constexpr uint32_t BF_SHAPE_SHIFT = 4;         // EDYNHIP_SHAPE_* in bits 4..7
 constexpr uint32_t BF_SHAPE_MASK = 0xF0u;
-constexpr uint32_t BF_ASLEEP = 0x100u;         // sleeping_tag: the body's island is asleep (island sleeping, solver.hip k_sleep_*)
+constexpr uint32_t BF_ASLEEP = 0x100u;         // sleeping_tag: the body's island is asleep (island sleeping, islands.hip k_sleep_*)
 constexpr uint32_t BF_NOSLEEP = 0x200u;        // sleeping_disabled_tag
 constexpr uint32_t BF_REMOVED = 0x400u;        // destroyed entity: the index stays reserved (edynhip_remove_bodies)
 // An edge (manifold, joint) sleeps when every procedural endpoint sleeps (an island sleeps as a whole).
@@ -77,7 +78,7 @@ struct Manifolds {
                                   // the narrowphase then reads the old points from there instead of a copy
     uint8_t *tree = nullptr;      // 1 = the island union-find hooked on this manifold: the marked manifolds (with the joints) are a
                                   // spanning forest of the contact graph, i.e. a certificate for the island labels - while none of
-                                  // them disappears, no island can have split and the labels are updated incrementally (solver.hip)
+                                  // them disappears, no island can have split and the labels are updated incrementally (islands.hip)
     // per point slot k (list order, newest first), five float4 at index pt_at(cap, k, m) of five INTERLEAVED base pointers (round 6: one
     // 320-byte record per manifold - pA pB nrm lnrm imp of point 0, then of point 1, ... - so a lane that reaches a manifold through an index
     // (the row preparation through the colour-sorted order, the narrowphase through prev_idx) pulls 3 lines instead of 20: a 16-byte gather
@@ -211,6 +212,28 @@ __host__ __device__ inline size_t pslot_at(uint32_t slot, uint32_t piece) {   //
     return (size_t)(p >> 5) * 192u + (piece << 6) + (slot & 63u);
 }
 
+// Development knobs: every EDYNHIP_* environment variable the library reads (A/B switches, overrides, developer output). They are
+// read in ONE place, read_knobs (capi.hip), whose table holds each knob's name, kind, default and meaning - when a context is created
+// (edynhip_ctx::knobs) and when a multi-device world is created (for world_serial / world_trace). The defaults are the table's: a Knobs
+// that read_knobs has not filled holds zeros. scripts/README.md lists the same rows.
+struct Knobs {
+    // schedules of the solve (solver.hip plan_solve)
+    bool dataflow, dataflow_pos, island_fused, mixed, df_xcd;
+    long df_lanes, df_waves, dfp_waves, df_nap;
+    std::string df_trace, dfp_trace;
+    long df_trace_step;
+    // the stages before it
+    bool speculate, inplace, bp_lists, bp_adapt, direct_compact, direct_sort, col_lds, np_fused;
+    long cc_compress;
+    bool poly_hint;
+    long poly_group, poly_group2;
+    // queries, read-back, multi-device worlds
+    long query_scan_ratio, records_direct;
+    bool world_serial, world_trace;
+    // developer output on stderr
+    bool bp_stats, pp_prof, tree_stats;
+};
+
 struct RayTree;   // raytree.hpp (raycast.hip, query_aabb.hip)
 struct QueryAabb;   // query_aabb.hip
 
@@ -301,6 +324,7 @@ struct StageTimer {
 
 struct edynhip_ctx {
     edynhip_config cfg{};
+    eh::Knobs knobs{};             // the development knobs as the environment had them when the context was created
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = true;
@@ -322,9 +346,9 @@ struct edynhip_ctx {
     uint2 *new_edges = nullptr;    // body pairs of manifolds created this step (incremental island update)
     uint32_t *new_edge_m = nullptr; //   and their manifold indices
     uint32_t prev_num_manifolds = 0;
-    uint32_t *col_keys = nullptr, *col_keys_sorted = nullptr;   // colour sort (counting sort, solver.hip k_cs_*)
+    uint32_t *col_keys = nullptr, *col_keys_sorted = nullptr;   // colour sort (counting sort, colouring.hip k_cs_*)
     uint32_t *cs_hist = nullptr, *cs_start = nullptr;            // [256 keys][blocks of 1024 manifolds]
-    uint32_t *cs_sup = nullptr;    // [16][256 keys] key counts of every 16 blocks (direct colour sort, solver.hip k_cs_*)
+    uint32_t *cs_sup = nullptr;    // [16][256 keys] key counts of every 16 blocks (direct colour sort, colouring.hip k_cs_*)
     uint32_t col_lds_edges = 0;   // listed edges k_col_rounds holds in LDS (set at the first colouring)
     uint64_t cc_full_steps = 0, cc_incremental_steps = 0;   // how the island labels were brought up to date, step by step (EDYNHIP_TREE_STATS)
     bool coop_launched = false;   // this context has made a cooperative launch (solver.hip launch_resident)
@@ -364,9 +388,8 @@ struct edynhip_ctx {
     float *state_host = nullptr;   // pinned mirror
     bool sleeping = false;         // EDYNHIP_FLAG_SLEEPING
     bool all_asleep = false;       // the last step left every procedural body asleep and nothing was edited since: steps are no-ops
-    bool solve_begin_done = false; // this step's k_cc_flatten already did k_solve_begin's work (solver.hip islands())
+    bool solve_begin_done = false; // this step's k_cc_flatten already did k_solve_begin's work (islands.hip islands())
     bool has_generic = false;      // some joint is a generic_constraint (k_prep_generic runs)
-    bool np_fused = true;          // narrowphase.hip: k_np_contacts (detect + merge in one pass) for the pairs collide() serves; EDYNHIP_NP_FUSED=0 at creation turns it off
     bool has_cylinder = false;     // some body is a cylinder_shape (narrowphase.hip k_np_detect_ext runs)
     // convex meshes and polyhedron bodies (mesh.hip)
     bool has_polyhedron = false;   // some body is a polyhedron_shape (k_update_rotated + k_np_detect_poly run)
@@ -431,11 +454,12 @@ struct edynhip_ctx {
     std::vector<uint64_t> host_group, host_mask;
     uint32_t *sleep_state = nullptr, *sleep_action = nullptr;   // per island label: reduction bits / decision
     double *sleep_since = nullptr;                              // per island label: stamp at which its timer started, < 0 = not running
-    // the timer that survives an island merge (solver.hip k_sleep_sizes / k_sleep_carry): last step's labels and body count, sizes of last
+    // the timer that survives an island merge (islands.hip k_sleep_sizes / k_sleep_carry): last step's labels and body count, sizes of last
     // step's islands, the biggest candidate per new label (size << 32 | ~old label), the carried stamps
     uint32_t *sleep_old_label = nullptr, *sleep_size = nullptr, sleep_prev_n = 0;
     unsigned long long *sleep_best = nullptr;
     double *sleep_carried = nullptr;
+    long df_solves = 0, dfp_solves = 0;   // dataflow velocity / position solves so far while a trace is asked for (EDYNHIP_DF_TRACE_STEP picks one; solver.hip DfTrace)
     int df_mode = -1;              // dataflow velocity solve: -1 = not probed yet, 0 = unavailable/disabled, 1 = in use
     uint32_t df_lanes = 0;         // resident waves of the dataflow velocity kernel
     uint32_t dfp_waves = 0;        // resident waves of the dataflow position kernel
@@ -480,6 +504,10 @@ int scan_u32(edynhip_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n);   /
 int debug_collide(edynhip_ctx *c, uint32_t n, const int32_t *st, const float *sp, const float *pos, const float *orn, float threshold,
                   float *out, uint32_t *count);
 int islands(edynhip_ctx *c);
+// colouring.hip: colours this step's new contacts and sorts the manifolds by (colour, point count). `between` is called once, after the
+// first counter publish is enqueued and before the host waits for it; *first_final: those counters were the final ones.
+int colour_contacts(edynhip_ctx *c, const std::function<void()> &between, bool *first_final);
+Knobs read_knobs();   // capi.hip: the only function that reads EDYNHIP_* variables
 inline EventSink event_sink(const edynhip_ctx *c) { return EventSink{c->events, c->event_count, c->event_cap, c->step_index}; }
 int restitution(edynhip_ctx *c);   // restitution.hip: solve_restitution, before gravity and the constraint solver (solver.cpp:397)
 int solve(edynhip_ctx *c);

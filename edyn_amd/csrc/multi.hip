@@ -277,7 +277,7 @@ struct Shard {
 
 class Pool {   // one persistent host thread per shard (a context is single-threaded; its step spins on its own counters)
 public:
-    explicit Pool(uint32_t n) : n_(n), serial_(getenv("EDYNHIP_WORLD_SERIAL") != nullptr) {   // (developer knob: every shard on the caller's thread)
+    Pool(uint32_t n, bool serial) : n_(n), serial_(serial) {   // (serial: developer knob EDYNHIP_WORLD_SERIAL=1, every shard on the caller's thread)
         if (!serial_) for (uint32_t r = 0; r < n; ++r) threads_.emplace_back([this, r] { loop(r); });
     }
     ~Pool() {
@@ -327,6 +327,7 @@ constexpr float kHorizon = 1.0f;            // cross-shard pairs further apart t
 
 struct edynhip_world {
     edynhip_config cfg{};
+    eh::Knobs knobs{};   // read when the world is created (world_serial, world_trace; every shard context reads its own)
     std::vector<int> devices;
     std::vector<Shard> shards;
     std::unique_ptr<Pool> pool;
@@ -432,7 +433,7 @@ int shard_filter_thunk(void *user, uint32_t body, uint32_t other) {
 // developer aid (EDYNHIP_WORLD_TRACE=1): wall time of the phases of a re-partition, to stderr
 struct PhaseTrace {
     bool on; std::chrono::steady_clock::time_point t0; const char *what;
-    explicit PhaseTrace(const char *w_) : on(getenv("EDYNHIP_WORLD_TRACE") != nullptr), t0(std::chrono::steady_clock::now()), what(w_) {}
+    PhaseTrace(const edynhip_world *w, const char *w_) : on(w->knobs.world_trace), t0(std::chrono::steady_clock::now()), what(w_) {}
     void mark(const char *phase) {
         if (!on) return;
         const auto t1 = std::chrono::steady_clock::now();
@@ -445,7 +446,7 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     Shard &s = w->shards[r];
     const HostScene &sc = w->scene;
     s.rc = EDYNHIP_OK; s.err.clear();
-    PhaseTrace trace("build_shard");
+    PhaseTrace trace(w, "build_shard");
     SH_HIP(s, hipSetDevice(s.device));
     const uint32_t n = sc.n;
     s.local_ids.clear(); s.owned_local.clear();
@@ -760,7 +761,7 @@ void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out) {
 
 // `only` (or nullptr = all): the shards to build; the others keep their contexts - their bodies, and therefore their local indices, are unchanged.
 int rebuild(edynhip_world *w, const Carry &carry, bool from_state, const std::vector<uint8_t> *only = nullptr) {
-    PhaseTrace trace("rebuild");
+    PhaseTrace trace(w, "rebuild");
     w->pool->run([&](uint32_t r) { if (!only || (*only)[r]) build_shard(w, r, carry, from_state); });
     EH_TRY(shard_error(w));
     trace.mark("build the shards (in parallel)");
@@ -786,7 +787,7 @@ int rebuild(edynhip_world *w, const Carry &carry, bool from_state, const std::ve
 int repartition(edynhip_world *w, bool sticky) {
     const HostScene &sc = w->scene;
     const uint32_t n = sc.n, W = (uint32_t)w->shards.size();
-    PhaseTrace trace(sticky ? "sticky re-partition" : "full re-partition");
+    PhaseTrace trace(w, sticky ? "sticky re-partition" : "full re-partition");
     w->pool->run([w, sticky](uint32_t r) { collect_shard(w, r, true, !sticky); });
     EH_TRY(shard_error(w));
     trace.mark("collect light state of every shard");
@@ -1120,12 +1121,13 @@ edynhip_world *edynhip_world_create(const edynhip_config *cfg, const int32_t *de
     for (uint32_t r = 0; r < num_devices; ++r) if (devices[r] < 0 || devices[r] >= ndev) return fail(EDYNHIP_ERR_INVALID, "edynhip_world_create: device ordinal out of range");
     edynhip_world *w = new edynhip_world();
     w->cfg = *cfg;
+    w->knobs = eh::read_knobs();
     w->devices.assign(devices, devices + num_devices);
     w->shards.resize(num_devices);
     for (uint32_t r = 0; r < num_devices; ++r) w->shards[r].device = devices[r];
     // several shards on ONE device (functional tests) must not promise that device to each of them
     for (uint32_t r = 0; r < num_devices; ++r) for (uint32_t q = 0; q < r; ++q) if (devices[q] == devices[r]) w->cfg.flags &= ~(uint32_t)EDYNHIP_FLAG_EXCLUSIVE_DEVICE;
-    w->pool.reset(new Pool(num_devices));
+    w->pool.reset(new Pool(num_devices, w->knobs.world_serial));
     w->shard_filters.resize(num_devices);
     for (uint32_t r = 0; r < num_devices; ++r) w->shard_filters[r] = edynhip_world::ShardFilter{w, r};
     w->stats.num_shards = num_devices;

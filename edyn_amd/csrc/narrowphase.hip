@@ -716,7 +716,7 @@ int debug_collide(edynhip_ctx *c, uint32_t n, const int32_t *st, const float *sp
             uint32_t stride = 0;
             for (const MeshDesc &md : c->host_meshes.desc) stride = std::max(stride, md.rot_size);
             const uint32_t chunk = 16384;
-            const int group = getenv("EDYNHIP_POLY_GROUP") ? atoi(getenv("EDYNHIP_POLY_GROUP")) : 8;   // (as narrowphase() below)
+            const int group = (int)c->knobs.poly_group;   // (as narrowphase() below)
             float4 *scratch = nullptr;
             e = hipMalloc((void **)&scratch, (size_t)chunk * 2 * stride * sizeof(float4));
             for (uint32_t first = 0; first < n && e == hipSuccess; first += chunk) {
@@ -741,7 +741,7 @@ int narrowphase(edynhip_ctx *c) {
     if (M == 0) return EDYNHIP_OK;
     const Staging st{c->np_ra, c->np_rb, c->np_rn, c->np_rnum};
     const bool staged_world = c->has_cylinder || c->has_polyhedron;
-    if (c->np_fused)
+    if (c->knobs.np_fused)
         hipLaunchKernelGGL(k_np_contacts, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->cfg.fixed_dt, c->sleeping, c->m[c->cur ^ 1], c->points_in_prev, c->np_rnum,
                            event_sink(c), staged_world);
     else
@@ -753,17 +753,17 @@ int narrowphase(edynhip_ctx *c) {
         const size_t cap = c->m[0].cap;
         uint32_t *const hints = pw + 3 * kPolyBins + 1 + 2 * cap;   // [2][cap]: one hint array per manifold array
         const PolyBins pb{pw, pw + kPolyBins, pw + 2 * kPolyBins, pw + 3 * kPolyBins, pw + 3 * kPolyBins + 1, pw + 3 * kPolyBins + 1 + cap, hints + (size_t)c->cur * cap};
-        static const bool use_hints = !(getenv("EDYNHIP_POLY_HINT") && getenv("EDYNHIP_POLY_HINT")[0] == '0');   // developer knob (A/B)
+        const bool use_hints = c->knobs.poly_hint;   // developer knob (A/B)
         hipLaunchKernelGGL(k_poly_count, dim3((M + 255) / 256), dim3(256), 0, c->stream, M, c->m[c->cur], c->b, c->sleeping, pb, c->meshes, hints + (size_t)(c->cur ^ 1) * cap,
                            !c->inplace_step, use_hints);
         hipLaunchKernelGGL(k_poly_scan, dim3(1), dim3(1024), 0, c->stream, pb);
         hipLaunchKernelGGL(k_poly_scatter, dim3((M + 255) / 256), dim3(256), 0, c->stream, M, pb);
         // developer knobs (A/B): EDYNHIP_POLY_GROUP=0 the round-4 form (k_np_detect_poly for polyhedron pairs too), =8 / 16 lanes per pair in the separating-axis kernel (default 8)
-        static const int group = getenv("EDYNHIP_POLY_GROUP") ? atoi(getenv("EDYNHIP_POLY_GROUP")) : 8;
+        const int group = (int)c->knobs.poly_group;
         if (group != 0) {
             const uint32_t waves = 5120;   // 20 per CU of an MI355X (the axes kernel runs five per SIMD): the grids stride over the pairs
-            static const int group2 = getenv("EDYNHIP_POLY_GROUP2") ? atoi(getenv("EDYNHIP_POLY_GROUP2")) : 4;   // lanes per surviving pair: 4 (default: 16 pairs per wave), 8 or 16
-            static const bool prof = getenv("EDYNHIP_PP_PROF") != nullptr;   // developer profile of the phases: printed every 100th step, per context (its counters live with the context: the shards of a multi-device world step on their own threads and devices)
+            const int group2 = (int)c->knobs.poly_group2;   // lanes per surviving pair: 4 (default: 16 pairs per wave), 8 or 16
+            const bool prof = c->knobs.pp_prof;   // developer profile of the phases: printed every 100th step, per context (its counters live with the context: the shards of a multi-device world step on their own threads and devices)
             unsigned long long *&prof_dev = c->pp_prof_dev;
             int &prof_calls = c->pp_prof_calls;
             if (prof && !prof_dev) { void *q = nullptr; EH_HIP(c, hipMalloc(&q, 128)); c->allocs.push_back(q); prof_dev = (unsigned long long *)q; EH_HIP(c, hipMemsetAsync(prof_dev, 0, 128, c->stream)); }
@@ -794,9 +794,9 @@ int narrowphase(edynhip_ctx *c) {
         }
         hipLaunchKernelGGL(k_np_detect_poly, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, st, c->meshes, pb, group != 0);
     }
-    if (!c->np_fused || staged_world)
+    if (!c->knobs.np_fused || staged_world)
         hipLaunchKernelGGL(k_np_merge, dim3((M + 63) / 64), dim3(64), 0, c->stream, M, c->m[c->cur], c->b, c->cfg.fixed_dt, c->sleeping, c->m[c->cur ^ 1], c->points_in_prev, st, event_sink(c),
-                           c->np_fused);
+                           c->knobs.np_fused);
     c->points_in_prev = false;
     EH_HIP(c, hipGetLastError());
     return EDYNHIP_OK;

@@ -351,7 +351,7 @@ static int scan_counts(edynhip_ctx *c, QueryAabb &q, uint32_t n, const uint32_t 
 static int qa_reserve(edynhip_ctx *c, uint32_t n, bool islands) {
     if (!c->qa) {
         c->qa = new QueryAabb();
-        if (const char *e = getenv("EDYNHIP_QUERY_SCAN_RATIO")) { const long v = atol(e); if (v > 0 && v < (1 << 20)) c->qa->scan_ratio = (uint32_t)v; }
+        { const long v = c->knobs.query_scan_ratio; if (v > 0 && v < (1 << 20)) c->qa->scan_ratio = (uint32_t)v; }   // developer knob EDYNHIP_QUERY_SCAN_RATIO
     }
     QueryAabb &q = *c->qa;
     if (!q.ctl) {

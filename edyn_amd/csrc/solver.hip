@@ -1,9 +1,9 @@
-// Islands, graph colouring, constraint-row preparation, the sequential-impulse (PGS) velocity solver,
-// integration, the position solver and the post-step derived state, as gfx950 kernels.
+// Constraint-row preparation, the sequential-impulse (PGS) velocity solver, integration, the position solver and the
+// post-step derived state, as gfx950 kernels, and the host function that schedules them (solve()). The island labels come
+// from islands.hip, the colours and the colour-sorted order from colouring.hip.
 //
 // Reference functions reproduced (arithmetic order kept):
-//   island labelling            src/edyn/simulation/island_manager.cpp:117-350 (connected components; static nodes do not connect)
-//   apply_gravity               include/edyn/sys/apply_gravity.hpp:12-17
+//   apply_gravity               include/edyn/sys/apply_gravity.hpp:12-17 (solve_begin_body, dstep.hpp)
 //   contact rows                src/edyn/constraints/contact_constraint.cpp:15-56
 //   point / hinge rows          src/edyn/constraints/point_constraint.cpp:9-46, hinge_constraint.cpp:26-67
 //   prepare_row                 src/edyn/constraints/constraint_row.cpp:6-22
@@ -14,10 +14,8 @@
 //                               hinge_constraint.cpp:180-213, island_solver.cpp:350-353,538-542
 //   update_aabbs / inertias     src/edyn/util/aabb_util.cpp:42-70, src/edyn/sys/update_inertias.cpp:12-24
 //
-//   sleeping                    src/edyn/simulation/island_manager.cpp:524-623 (k_sleep_*)
-//
 // What is NOT in the reference: within an island the reference sweeps rows strictly sequentially
-// (Gauss-Seidel). Here the contact graph is edge-coloured so that the manifolds of one colour share no
+// (Gauss-Seidel). Here the contact graph is edge-coloured (colouring.hip) so that the manifolds of one colour share no
 // procedural body, and every body meets its manifolds in colour order. Per iteration: joints by colour, then
 // contacts by colour; a manifold sweeps its normal rows and then its friction rows (the friction circle uses
 // the normal impulse just updated, as in the reference); the reference's global "all rows, then all friction
@@ -28,771 +26,10 @@
 //   * per colour (scenes with joints, or when the resident-grid launch is refused): one launch per colour with one
 //     manifold per lane (k_contact_solve, k_joint_solve, k_pos_contacts, k_pos_joints).
 #include <mutex>
-#include "ctx.hpp"
+#include "dstep.hpp"
 #include "dpolyhedron.hpp"
 
 namespace eh {
-using namespace dm;
-
-static inline uint32_t blocks(uint32_t n, uint32_t bs) { return (n + bs - 1) / bs; }
-
-DI bool is_dynamic(uint32_t flags) { return (flags & BF_KIND_MASK) == EDYNHIP_KIND_DYNAMIC; }
-constexpr uint32_t kCsBlock = 1024, kCsKeys = 256, kCsDirectBlocks = 256, kCsSuper = 16;   // the colour sort (k_cs_*)
-// Edge priority for the colouring rounds: lower edge index wins, which reproduces sequential first-fit
-// colouring in canonical pair order (near-optimal colour counts on stacked scenes: max degree or +1) at the
-// price of more rounds when a whole scene is coloured from scratch; steady state only colours new edges.
-DI uint64_t edge_prio(uint32_t e) { return (uint64_t)(0xFFFFFFFFu - e); }
-
-// ------------------------------------------------------------------ islands (lock-free union-find)
-// Links always point to a SMALLER body index and only ever move towards the root, so any value ever stored in
-// parent[x] is an ancestor of x (or x itself) for the rest of the launch. Plain, possibly stale (per-CU L1 / per-XCD
-// L2) loads are therefore safe for the walks: a stale value is merely a longer path. Only the hook itself must be
-// exact - it is a device-scope compare-and-swap on the true memory value, and on failure the walk continues from the
-// fresh value it returned. (Agent-scope atomic loads here were measured ~8x slower: every step went to the fabric.)
-DI uint32_t cc_find(uint32_t *parent, uint32_t x) {
-    uint32_t p = parent[x];
-    while (p != x) {
-        const uint32_t gp = parent[p];
-        if (gp != p) parent[x] = gp;   // path halving; racing writers all store ancestors
-        x = p; p = gp;
-    }
-    return x;
-}
-DI bool cc_union(uint32_t *parent, uint32_t a, uint32_t b) {   // true: this call joined two trees (the edge certifies the union)
-    uint32_t ra = cc_find(parent, a), rb = cc_find(parent, b);
-    while (ra != rb) {
-        if (ra < rb) { const uint32_t t = ra; ra = rb; rb = t; }   // hook the larger root under the smaller
-        const uint32_t seen = atomicCAS(&parent[ra], ra, rb);
-        if (seen == ra) return true;
-        ra = cc_find(parent, seen);   // ra was no longer a root: continue from what it points to now
-        rb = cc_find(parent, rb);
-    }
-    return false;
-}
-// Island labels are maintained incrementally, and the HOST picks the mode from counters it fetched with the pair count:
-//   CC_SKIP         unchanged pair set (in-place step): nothing is launched;
-//   CC_INCREMENTAL  no island can have split: start from last step's labels (roots = a depth-1 forest), hook the new edges;
-//   CC_FULL         recompute over all joints and manifolds (scene edits, or a certificate manifold disappeared).
-// "No island can have split" is decided with a CERTIFICATE: every union the forest ever performed was made on a particular
-// edge - a joint, or a manifold, which is then marked (Manifolds::tree). The marked edges form a spanning forest of the
-// contact graph, so as long as every marked manifold of the previous array is still in this step's pair set
-// (Counters::tree_found == tree_total, counted by k_bp_pairs while it re-tests the existing pairs) the components are intact,
-// whatever other pairs went away. Manifolds that carry contact points are hooked first and separated AABBs almost always
-// belong to manifolds without points, so on a settled pile the full recompute (~100 us: its cost is the depth of the
-// initial forest) went from most steps to almost none. (Round 2 recomputed whenever ANY pair disappeared.)
-enum { CC_SKIP = 0, CC_INCREMENTAL = 1, CC_FULL = 2 };
-DI void cc_count_marks(uint32_t marks, Counters *cnt) {   // every lane of the wave calls this
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) marks += __shfl_xor(marks, off);
-    if ((threadIdx.x & 63) == 0 && marks) atomicAdd(&cnt->tree_marks, marks);
-}
-// CC_FULL only: every body starts at its smallest dynamic lower-index neighbour it has CONTACT POINTS with (its manifolds
-// with lower-index partners are the contiguous segment [seg_start, seg_end) of the sorted array). Links point to smaller
-// indices, so this is a valid forest and most unions below find their roots already merged. Clears the segment's marks.
-// (Round 6, built, measured and withdrawn - profiles/r06_tree_repair_experiment/, the patch is kept there: LOCAL REPAIR of the certificate. k_bp_pairs
-//  listed the marked manifolds the new pair set drops, an extra workgroup of k_bp_compact looked for a replacement path a - c - b over manifolds
-//  that exist in both arrays (c among a's lower-index partners) and marked it, the host then kept the incremental mode. Bit-exact, but a step
-//  drops SEVERAL certificate manifolds and every one needs its path: 8 of 135 relabelling steps repaired on the headline pile, 20 of 384 on
-//  mixed32k, 13 of 129 on islands256k, none on the polyhedron heap, which paid 4 % for the listing. EDYNHIP_TREE_STATS=1 prints the counts.)
-// (Round 6, measured and dropped: offering the edges in classes of decreasing STABILITY - manifolds whose oldest point has lived for 32 steps,
-//  then the other manifolds with points, then the pointless ones - so that the certificate consists of long-lived contacts. The number of
-//  steps that relabel in full did not move (mixed32k 372 against 373 of 440, pile32k 127 / 128, islands256k 277 / 277, the polyhedron heap
-//  every step either way) and the two kernels got slower (k_cc_hook_bodies 55 -> 70 us): what breaks a certificate on these scenes is not
-//  a young contact flickering but some long-lived pair of 32 768 bodies separating, in nearly every step. scripts/runs/r6k.sh.)
-__global__ void k_cc_init(uint32_t n, uint32_t *forest, Counters *cnt, Manifolds mf, uint32_t M, const uint32_t *__restrict__ flags) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) cnt->num_islands = 0;
-    uint32_t marks = 0;
-    if (i < n) {
-        uint32_t parent = i;
-        if (M && is_dynamic(flags[i])) {
-            for (uint32_t s = mf.seg_start[i], e = mf.seg_end[i]; s < e; ++s) {
-                const uint32_t lo = (uint32_t)(mf.skey[s] >> 1);
-                uint8_t mark = 0;
-                if (parent == i && (mf.info[s] & 0xFF) != 0 && is_dynamic(flags[lo])) { parent = lo; mark = 1; marks = 1; }
-                mf.tree[s] = mark;
-            }
-        }
-        forest[i] = parent;
-    }
-    cc_count_marks(marks, cnt);
-}
-// CC_FULL, between the initial forest and the unions (round 5): every body's link goes straight to its root. The initial forest of a pile
-// is a set of chains ~100 links deep (each body under its lowest lower-index partner); without this pass every union of k_cc_hook_bodies
-// walks such a chain twice. The walks halve the paths they pass, so a second pass costs little where the first has been.
-__global__ void k_cc_compress(uint32_t n, uint32_t *forest, const uint32_t *__restrict__ flags) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && is_dynamic(flags[i])) forest[i] = cc_find(forest, i);   // (a racing hook cannot exist here: only finds run in this launch)
-}
-__global__ void k_cc_hook(uint32_t M, const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                          const uint32_t *__restrict__ flags, uint32_t *island) {   // joints (CC_FULL): edges that only an edit removes
-    uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= M) return;
-    uint32_t a = bA[e], b = bB[e];
-    if (is_dynamic(flags[a]) && is_dynamic(flags[b])) (void)cc_union(island, a, b);
-}
-// Vertex-centric hooking for the full recompute: one lane per body walks the contiguous run of manifolds in which it
-// is the higher-index partner. All unions of one body are issued by one lane in sequence, so lanes do not fight over
-// the same root the way one-lane-per-edge does when a body has 6-12 partners. Manifolds with contact points first.
-__global__ void k_cc_hook_bodies(uint32_t n, Manifolds mf, uint32_t M, const uint32_t *__restrict__ flags, uint32_t *island, Counters *cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t marks = 0;
-    if (i < n && M != 0 && is_dynamic(flags[i])) {
-        const uint32_t s0 = mf.seg_start[i], s1 = mf.seg_end[i];
-        auto hook = [&](uint32_t s) {
-            const uint32_t lo = (uint32_t)(mf.skey[s] >> 1);
-            if (!is_dynamic(flags[lo])) return;
-            if (island[i] == island[lo]) return;   // both under the same node: one tree already (two loads instead of two walks; most edges of a pile end here)
-            if (cc_union(island, i, lo)) { mf.tree[s] = 1; ++marks; }
-        };
-        // the manifolds with contact points first; the others are remembered (a bit each: an owner keeps at most kOwnCap = 64 in its segment,
-        // longer segments take the plain second pass) and visited afterwards without reading the point counts again
-        uint64_t later = 0;
-        const bool fits = s1 - s0 <= 64u;
-        for (uint32_t s = s0; s < s1; ++s) {
-            if ((mf.info[s] & 0xFF) != 0) hook(s);
-            else if (fits) later |= 1ull << (s - s0);
-        }
-        if (fits) for (; later; later &= later - 1) hook(s0 + (uint32_t)__ffsll((long long)later) - 1u);
-        else for (uint32_t s = s0; s < s1; ++s) if ((mf.info[s] & 0xFF) == 0) hook(s);
-    }
-    cc_count_marks(marks, cnt);
-}
-__global__ void k_cc_hook_new(const uint2 *__restrict__ edges, const uint32_t *__restrict__ edge_m, uint8_t *tree, const uint32_t *__restrict__ flags,
-                              uint32_t *island, Counters *cnt) {   // CC_INCREMENTAL: `island` holds last step's labels
-    const uint32_t n = cnt->num_new;
-    if (blockIdx.x == 0 && threadIdx.x == 0) cnt->num_islands = 0;
-    uint32_t marks = 0;
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-        uint2 ed = edges[e];
-        if (is_dynamic(flags[ed.x]) && is_dynamic(flags[ed.y]) && cc_union(island, ed.x, ed.y)) { tree[edge_m[e]] = 1; ++marks; }
-    }
-    cc_count_marks(marks, cnt);
-}
-// The per-body start of the solve (k_solve_begin: gravity, zeroed deltas, hand-off chain heads) - also folded into k_cc_flatten, the
-// per-body kernel that precedes it, when nothing that runs in between reads velocities or sleep flags (no island sleeping, no restitution).
-DI void solve_begin_body(uint32_t i, Bodies &b, float dt, uint32_t *first_slot) {
-    first_slot[i] = 0xFFFFFFFFu;
-    uint32_t fl = b.flags[i];
-    float inv_m = 0;
-    if (is_dynamic(fl)) {
-        inv_m = B_POS(b, i).w;
-        f3 g = from4(b.grav[i]);
-        if (!(g.x == 0 && g.y == 0 && g.z == 0) && !(fl & BF_ASLEEP)) {   // apply_gravity.hpp:13 excludes sleeping bodies
-            f3 v = from4(b.linvel[i]);
-            v += g * dt;
-            b.linvel[i] = to4(v, 0);
-        }
-    }
-    B_DV(b, i) = make_float4(0, 0, 0, inv_m);
-    B_DW(b, i) = make_float4(0, 0, 0, 0);
-}
-enum { SL_FAST = 1, SL_DISABLED = 2, SL_HAS_ASLEEP = 4, SL_HAS_AWAKE = 8, SL_WAKE = 16, SL_SPLIT = 32 };   // island state bits (k_sleep_*)
-enum { SLA_KEEP = 0, SLA_AWAKE = 1, SLA_SLEEP = 2 };
-// split_state (island sleeping, full relabel only): a body whose root differs from the root of last step's root of its island is a
-// part of an island that fell apart - both parts are marked, k_sleep_decide starts their timers again (split_islands,
-// island_manager.cpp:411-447: every part of a split island ends up with an empty sleep_timestamp).
-template <bool BEGIN>
-__global__ void k_cc_flatten(uint32_t n, const uint32_t *__restrict__ flags, uint32_t *island, uint32_t *label, Counters *cnt, int mode, Bodies b, float dt, uint32_t *first_slot,
-                             uint32_t *split_state) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) cnt->tree_total = (mode == CC_FULL ? 0u : cnt->tree_total) + cnt->tree_marks;   // the hooks are done (kernel boundary)
-    uint32_t root = 0;
-    if (i < n) {
-        uint32_t r = cc_find(island, i);
-        if (split_state && is_dynamic(flags[i]) && !(flags[i] & BF_REMOVED)) {
-            const uint32_t o = label[i];   // last step's root of this body's island (a full relabel works on a scratch forest: `label` is still last step's here)
-            if (o < n && is_dynamic(flags[o]) && !(flags[o] & BF_REMOVED)) {
-                const uint32_t ro = cc_find(island, o);
-                if (ro != r) { atomicOr(&split_state[r], (uint32_t)SL_SPLIT); atomicOr(&split_state[ro], (uint32_t)SL_SPLIT); }
-            }
-        }
-        label[i] = r;
-        root = (r == i && is_dynamic(flags[i])) ? 1u : 0u;
-        if (BEGIN) solve_begin_body(i, b, dt, first_slot);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) root += __shfl_xor(root, off);
-    if ((threadIdx.x & 63) == 0 && root) atomicAdd(&cnt->num_islands, root);
-}
-
-// ------------------------------------------------------------------ island sleeping (island_manager.cpp:524-623)
-// Islands are identified by their label (lowest body index). Per step, after the labels: (1) reduce every island's
-// bodies into state bits, (2) mark the islands that received a manifold created this step, (3) one lane per island
-// decides - wake (new edge, or sleeping and awake bodies merged), keep sleeping, run / restart the timer, go to sleep
-// once the timer has run for more than island_time_to_sleep (measured on the step time stamps, ctx.hpp sim_clock) - (4) every body applies its island's decision (put_to_sleep zeroes velocities).
-// merge_islands (island_manager.cpp:297-350): the BIGGEST of the islands that merge - nodes + edges - survives with its sleep timer.
-// Labels are lowest body indices, so the surviving timer is carried to the merged island's label: per new island, the timer of the biggest
-// of last step's islands it consists of; size = its procedural bodies + the edges it had before this step (manifolds that persist from
-// the previous array, joints), ties: the lowest old label (the checker's coloured order counts the same; pinned to the engine by
-// tests/test_reference_engine.py::test_island_merge_keeps_the_bigger_islands_sleep_timer_like_the_real_engine). Three small passes
-// in the steps of a world with island sleeping that relabel: k_sleep_sizes (sizes of last step's islands, keyed by last step's labels -
-// a copy taken before the hooks, the union-find halves paths in place), the candidate maximum in k_sleep_scan, k_sleep_carry.
-struct SleepMerge { const uint32_t *old_label; uint32_t prev_n; uint32_t *size; unsigned long long *best; double *carried; };
-DI void add_by_label(uint32_t label, uint32_t amount, uint32_t *dst) {   // every lane of the wave calls this (amount 0 = nothing): one atomic per distinct label and wave
-    uint64_t todo = __ballot(amount != 0);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t l = (uint32_t)__shfl((int)label, leader);
-        const bool mine = amount != 0 && label == l;
-        uint32_t sum = mine ? amount : 0u;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&dst[l], sum);
-        todo &= ~__ballot(mine);
-    }
-}
-DI void or_by_label(uint32_t label, uint32_t bits, uint32_t *dst) {   // every lane of the wave calls this (bits 0 = nothing): one atomic per distinct label and wave
-    // (one lane per body OR-ing into its island's word serialises on that word: a 32k-body pile - one island - spent 0.4 ms per step here)
-    uint64_t todo = __ballot(bits != 0);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t l = (uint32_t)__shfl((int)label, leader);
-        const bool mine = bits != 0 && label == l;
-        uint32_t all = mine ? bits : 0u;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) all |= (uint32_t)__shfl_xor((int)all, off);
-        // the word only gains bits while this kernel runs (k_sleep_decide zeroed it): a stale read can cost a redundant atomic, never a lost bit
-        if ((int)(threadIdx.x & 63) == leader && (__hip_atomic_load(&dst[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & all) != all) atomicOr(&dst[l], all);
-        todo &= ~__ballot(mine);
-    }
-}
-__global__ void k_sleep_sizes(uint32_t n, Bodies b, Manifolds mf, uint32_t M, Joints j, SleepMerge sm) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t label = 0, amount = 0;
-    if (i < n && i < sm.prev_n && is_dynamic(b.flags[i]) && !(b.flags[i] & BF_REMOVED)) {
-        label = sm.old_label[i];
-        amount = 1;
-        if (M) for (uint32_t s = mf.seg_start[i], e = mf.seg_end[i]; s < e; ++s) amount += mf.prev_idx[s] != 0xFFFFFFFFu ? 1u : 0u;   // this body's manifolds (it is their owner) that existed before this step
-        if (label >= n) amount = 0;
-    }
-    add_by_label(label, amount, sm.size);
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < j.n; e += gridDim.x * blockDim.x) {   // joints (few): plain atomics
-        const uint32_t a = j.bodyA[e], bb = j.bodyB[e], x = is_dynamic(b.flags[a]) ? a : bb;
-        if (x < sm.prev_n && is_dynamic(b.flags[x]) && sm.old_label[x] < n) atomicAdd(&sm.size[sm.old_label[x]], 1u);
-    }
-}
-__global__ void k_sleep_carry(uint32_t n, Bodies b, SleepMerge sm, const double *__restrict__ since) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long key = sm.best[i];
-    sm.best[i] = 0ull; sm.size[i] = 0u;   // armed for the next relabelling step
-    sm.carried[i] = key ? since[~(uint32_t)key] : -1.0;
-}
-__global__ void k_sleep_scan(uint32_t n, Bodies b, uint32_t *state, SleepMerge sm) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t label = 0, bits = 0;
-    if (i < n) {
-        const uint32_t fl = b.flags[i];
-        if (is_dynamic(fl)) {
-            label = b.island[i];
-            // one of last step's island roots: a candidate for the timer of the island it is in now
-            if (sm.best && i < sm.prev_n && !(fl & BF_REMOVED) && sm.old_label[i] == i)
-                atomicMax(&sm.best[label], ((unsigned long long)sm.size[i] << 32) | (unsigned long long)(~i));
-            const f3 v = from4(b.linvel[i]), w = from4(b.angvel[i]);
-            const float lin = 0.005f, ang = 3.1415926535897932384626433832795029f / 48.0f;   // config/constants.hpp:41-42
-            bits = (fl & BF_ASLEEP) ? SL_HAS_ASLEEP : SL_HAS_AWAKE;
-            if (length_sqr(v) > lin * lin || length_sqr(w) > ang * ang) bits |= SL_FAST;
-            if (fl & BF_NOSLEEP) bits |= SL_DISABLED;
-        }
-    }
-    or_by_label(label, bits, state);
-}
-__global__ void k_sleep_edges(const uint2 *__restrict__ edges, const Counters *cnt, const uint32_t *__restrict__ label, uint32_t *state) {
-    const uint32_t n = cnt->num_new;
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x)
-        atomicOr(&state[label[edges[e].x]], (uint32_t)SL_WAKE);   // .x = the pair's owner: always procedural
-}
-__global__ void k_sleep_decide(uint32_t n, Bodies b, uint32_t *state, uint32_t *action, double *since, double now, const double *__restrict__ carried) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t s = state[i];
-    state[i] = 0;
-    if (!is_dynamic(b.flags[i]) || b.island[i] != i) { since[i] = -1.0; return; }
-    if (carried) since[i] = carried[i];   // a relabelling step: the timer of the biggest island this one is made of (k_sleep_carry)
-    if (s & SL_SPLIT) since[i] = -1.0;   // a part of an island that split: the timer starts again
-    const bool wake = (s & SL_WAKE) || ((s & SL_HAS_ASLEEP) && (s & SL_HAS_AWAKE));
-    if ((s & SL_HAS_ASLEEP) && !(s & SL_HAS_AWAKE) && !wake) { action[i] = SLA_KEEP; return; }
-    uint32_t a = SLA_AWAKE;
-    if (!(s & SL_DISABLED) && !(s & SL_FAST)) {
-        const double t0 = since[i];
-        if (!(t0 >= 0.0)) since[i] = now;                                    // not running (a negative value or the all-ones fill)
-        else if (now - t0 > 2.0) { a = SLA_SLEEP; since[i] = -1.0; }         // island_time_to_sleep, constants.hpp:48
-    } else since[i] = -1.0;
-    action[i] = a;
-}
-__global__ void k_sleep_apply(uint32_t n, Bodies b, const uint32_t *__restrict__ action, Counters *cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t awake = 0;
-    if (i < n) {
-        uint32_t fl = b.flags[i];
-        if (is_dynamic(fl)) {
-            const uint32_t a = action[b.island[i]];
-            if (a == SLA_AWAKE) { if (fl & BF_ASLEEP) { fl &= ~BF_ASLEEP; b.flags[i] = fl; } }
-            else if (a == SLA_SLEEP) {
-                fl |= BF_ASLEEP; b.flags[i] = fl;
-                b.linvel[i] = make_float4(0, 0, 0, 0); b.angvel[i] = make_float4(0, 0, 0, 0);
-            }
-            awake = (fl & BF_ASLEEP) ? 0u : 1u;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) awake += __shfl_xor(awake, off);
-    if ((threadIdx.x & 63) == 0 && awake) atomicAdd(&cnt->num_awake, awake);
-}
-
-// ------------------------------------------------------------------ colouring
-// In every island that has an edge to colour in this step (a new or re-activated contact) the top colour carried over from the last
-// step is released and first-fit again, so colour classes freed by vanished contacts are reclaimed when the island next changes and
-// the colour count (= dependent hops per sweep) does not drift upwards - while an island in which nothing happened keeps its
-// colouring untouched (4096 settled mini-piles: nothing to recolour). Per ISLAND, not per world: an island is coloured - and
-// therefore solved - the same way whatever else the world holds, so a shard of the world (edyn_amd/parallel.py) steps exactly like
-// the whole. k_col_tops finds each island's top colour (+ 1; .x) and whether it has an uncoloured active edge (.y), k_col_prepare releases.
-__device__ __forceinline__ uint32_t manifold_label(uint32_t a, uint32_t b, uint32_t fa, const uint32_t *__restrict__ island) { return island[is_dynamic(fa) ? a : b]; }
-__global__ void __launch_bounds__(1024) k_col_tops(uint32_t M, const uint32_t *__restrict__ info, const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                                                   const uint32_t *__restrict__ flags, const uint32_t *__restrict__ island, uint2 *isl_top, uint32_t *cs_sup) {
-    __shared__ uint32_t s_label[16], s_top[16];
-    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    // (first kernel of the colouring chain: also clears the colour sort's super-block key counts, k_cs_hist<true>)
-    for (uint32_t g = m; g < (kCsDirectBlocks / kCsSuper) * kCsKeys; g += gridDim.x * blockDim.x) cs_sup[g] = 0u;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    uint32_t label = 0xFFFFFFFFu, top = 0;
-    if (m < M) {
-        const uint32_t in = info[m], np = in & 0xFF, col = in >> 8;
-        const uint32_t a = bA[m], b = bB[m], fa = flags[a], fb = flags[b];
-        if (np > 0 && !edge_asleep(fa, fb)) {
-            const uint32_t l = manifold_label(a, b, fa, island);
-            if (col != kNoColour) { label = l; top = col + 1; }
-            else isl_top[l].y = 1u;   // the island has something to colour in this step (identical plain stores)
-        }
-    }
-    // Neighbours in the canonical order mostly share their island. A wave of one island hands its maximum to the workgroup, which
-    // issues one atomic per run of equal labels (a big island: one per 1024 manifolds instead of thousands on one address); a wave
-    // that spans islands issues one atomic per island it touches. A plain look comes first: once an island's top colour has landed
-    // the others have nothing to add.
-    auto post = [&](uint32_t l, uint32_t t) { if (__atomic_load_n(&isl_top[l].x, __ATOMIC_RELAXED) < t) atomicMax(&isl_top[l].x, t); };
-    uint64_t todo = __ballot(top != 0);
-    uint32_t w_label = 0xFFFFFFFFu, w_top = 0;
-    if (todo) {
-        const uint32_t l0 = __shfl(label, __ffsll((long long)todo) - 1);
-        if (__ballot(top != 0 && label == l0) == todo) {   // one island
-            uint32_t t = top;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) t = max(t, (uint32_t)__shfl_xor(t, off));
-            w_label = l0; w_top = t;
-        } else {
-            while (todo) {
-                const uint32_t leader = (uint32_t)__ffsll((long long)todo) - 1, l = __shfl(label, leader);
-                const bool mine = top != 0 && label == l;
-                uint32_t t = mine ? top : 0;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) t = max(t, (uint32_t)__shfl_xor(t, off));
-                if (lane == leader) post(l, t);
-                todo &= ~__ballot(mine);
-            }
-        }
-    }
-    if (lane == 0) { s_label[wave] = w_label; s_top[wave] = w_top; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t l = 0xFFFFFFFFu, t = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (s_top[w] == 0) continue;
-            if (s_label[w] != l) { if (t) post(l, t); l = s_label[w]; t = 0; }
-            t = max(t, s_top[w]);
-        }
-        if (t) post(l, t);
-    }
-}
-__global__ void __launch_bounds__(1024) k_col_prepare(uint32_t M, uint32_t *__restrict__ info, const uint32_t *__restrict__ bA,
-                              const uint32_t *__restrict__ bB, const uint32_t *__restrict__ flags, uint64_t *used,
-                              uint64_t *best0, uint64_t *best1, Counters *cnt, const uint32_t *__restrict__ island, const uint2 *__restrict__ isl_top,
-                              uint32_t *unc_list) {
-    uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t unc = 0;
-    if (m < M) {
-        uint32_t in = info[m];
-        uint32_t np = in & 0xFF, col = in >> 8;
-        const uint32_t a = bA[m], b = bB[m];
-        const uint32_t fa = flags[a], fb = flags[b];
-        // a sleeping manifold is out of the solve but keeps (and blocks) its colour for when its island wakes
-        const bool asleep = edge_asleep(fa, fb);
-        if (np > 0 && col != kNoColour && !asleep) {
-            const uint2 top = isl_top[manifold_label(a, b, fa, island)];
-            if (top.y && top.x >= 2 && col + 1 == top.x) { col = kNoColour; info[m] = np | (kNoColour << 8); }
-        }
-        if (np > 0) {
-            bool da = is_dynamic(fa), db = is_dynamic(fb);
-            if (col != kNoColour) {
-                if (da) atomicOr((unsigned long long *)&used[a], 1ull << col);
-                if (db) atomicOr((unsigned long long *)&used[b], 1ull << col);
-            } else if (!asleep) {
-                unc = 1;
-                if (da) { best0[a] = 0; best1[a] = 0; }
-                if (db) { best0[b] = 0; best1[b] = 0; }
-            }
-        }
-    }
-    // list the uncoloured edges for k_col_rounds (beyond its capacity only the count matters): one pair of atomics per WORKGROUP - a
-    // restless scene has an uncoloured edge in almost every wave, and thousands of atomics on one cache line cost more than the kernel
-    __shared__ uint32_t wcount[16], wbase;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t mask = __ballot(unc != 0);
-    if (lane == 0) wcount[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) total += wcount[w];
-        wbase = total ? atomicAdd(&cnt->unc_count, total) : 0u;
-        if (total) atomicAdd(&cnt->uncoloured, total);
-    }
-    __syncthreads();
-    if (unc) {
-        uint32_t at = wbase + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        for (uint32_t w = 0; w < wave; ++w) at += wcount[w];
-        if (at < kColUncCap) unc_list[at] = m;
-    }
-}
-// The rounds for a list of uncoloured edges that one workgroup can hold - the steady state: some hundred (a restless heap: some
-// thousand) new contacts per step - run in one workgroup with workgroup barriers between the phases instead of two launches per
-// round; same rule, same result as k_col_best / k_col_assign. The edges' endpoints sit in LDS (index | dynamic << 31), the list is
-// compacted as edges take their colour (a round only visits what is still uncoloured). The endpoint marks carry the round in their upper
-// half - (round + 1) << 32 | priority - so a mark of an earlier round loses against any mark of this one and nothing has to be zeroed
-// between rounds (round 5: the workgroup is bound by the memory requests one CU can issue - a restless heap of polyhedra lists 15 000
-// edges per step and still has two thirds of them after three rounds; the zeroing stores were two of six requests per edge and round).
-// Longer lists, and what is left after max_rounds, go to the multi-block rounds (the host sees cnt->uncoloured != 0).
-__global__ void __launch_bounds__(1024) k_col_rounds(uint32_t *info, const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                                                     const uint32_t *__restrict__ flags, uint64_t *best0, uint64_t *best1, uint64_t *used, Counters *cnt,
-                                                     uint32_t *list, uint32_t cap, uint32_t max_rounds) {
-    extern __shared__ uint32_t col_lds[];   // ea[cap], eb[cap]
-    uint32_t *ea = col_lds, *eb = col_lds + cap;
-    __shared__ uint32_t live, wr;
-    const uint32_t n0 = cnt->unc_count;
-    if (n0 == 0 || n0 > cap) { if (threadIdx.x == 0) cnt->col_wg_rounds = 0; return; }
-    for (uint32_t e = threadIdx.x; e < n0; e += blockDim.x) {
-        const uint32_t m = list[e], a = bA[m], b = bB[m];
-        ea[e] = a | (is_dynamic(flags[a]) ? 0x80000000u : 0u);
-        eb[e] = b | (is_dynamic(flags[b]) ? 0x80000000u : 0u);
-    }
-    if (threadIdx.x == 0) live = n0;
-    __syncthreads();
-    auto ld = [](const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };   // other waves' stores: not through a stale L1 line
-    auto ld32 = [](const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    uint32_t round = 0;
-    for (; round < max_rounds; ++round) {
-        const uint32_t n = live;
-        if (n == 0) break;
-        uint64_t *cur = best0;
-        const uint64_t stamp = (uint64_t)(round + 1u) << 32;   // (edge_prio fits the lower half)
-        for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {           // phase 1: every endpoint learns its best uncoloured edge
-            const uint64_t pr = stamp | edge_prio(list[e]);
-            const uint32_t a = ea[e], b = eb[e];
-            if (a >> 31) atomicMax((unsigned long long *)&cur[a & 0x7FFFFFFFu], pr);
-            if (b >> 31) atomicMax((unsigned long long *)&cur[b & 0x7FFFFFFFu], pr);
-        }
-        if (threadIdx.x == 0) wr = 0;
-        __threadfence_block(); __syncthreads();   // one workgroup, one CU: its stores only have to reach L2 before the other waves' (atomic) loads
-        for (uint32_t base = 0; base < n; base += blockDim.x) {           // phase 2: edges that are best at both ends take a colour, the others stay listed
-            const uint32_t e = base + threadIdx.x;
-            bool keep = false;
-            uint32_t m = 0, a = 0, b = 0;
-            if (e < n) {
-                m = list[e]; a = ea[e]; b = eb[e];
-                const bool da = a >> 31, db = b >> 31;
-                const uint32_t ia = a & 0x7FFFFFFFu, ib = b & 0x7FFFFFFFu;
-                const uint64_t pr = stamp | edge_prio(m);
-                if ((da && ld(&cur[ia]) != pr) || (db && ld(&cur[ib]) != pr)) keep = true;
-                else {
-                    const uint64_t busy = (da ? ld(&used[ia]) : 0ull) | (db ? ld(&used[ib]) : 0ull);
-                    const uint64_t avail = ~busy & ((1ull << kSerialColour) - 1ull);
-                    const uint32_t c = avail ? (uint32_t)__ffsll((long long)avail) - 1 : kSerialColour;   // nothing free: the serial bucket
-                    info[m] = (ld32(&info[m]) & 0xFF) | (c << 8);
-                    if (da) atomicOr((unsigned long long *)&used[ia], 1ull << c);
-                    if (db) atomicOr((unsigned long long *)&used[ib], 1ull << c);
-                }
-            }
-            __syncthreads();   // this block of the list has been read: its survivors may now be written over the front of it
-            const uint64_t mask = __ballot(keep);
-            if (mask) {
-                const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__ffsll((long long)mask) - 1;
-                uint32_t at = 0;
-                if (lane == leader) at = atomicAdd(&wr, (uint32_t)__popcll(mask));
-                at = __shfl(at, leader) + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-                if (keep) { list[at] = m; ea[at] = a; eb[at] = b; }
-            }
-        }
-        __threadfence_block(); __syncthreads();
-        if (threadIdx.x == 0) live = wr;
-        __syncthreads();
-    }
-    const uint32_t left = live;
-    if (left) {   // handed to the multi-block rounds, which start from clean marks in both arrays
-        for (uint32_t e = threadIdx.x; e < left; e += blockDim.x) {
-            const uint32_t a = ea[e], b = eb[e];
-            if (a >> 31) { best0[a & 0x7FFFFFFFu] = 0; best1[a & 0x7FFFFFFFu] = 0; }
-            if (b >> 31) { best0[b & 0x7FFFFFFFu] = 0; best1[b & 0x7FFFFFFFu] = 0; }
-        }
-    }
-    if (threadIdx.x == 0) { cnt->uncoloured = left; cnt->col_wg_rounds = round; }
-}
-// Round 6, an experiment kept behind EDYNHIP_COL_LDS=1 (measured: 3 % faster on the polyhedron heap, 1-2 us SLOWER per step on every pile - the
-// 159 KB of LDS it asks for and its clearing - so k_col_rounds above stays the default; the two are compared by
-// test_colouring_rounds_in_lds_and_in_global_memory_colour_alike): the same rounds with the endpoint marks in LDS. The kernel above spends its time on the memory requests one CU can issue - eight
-// scattered 8-byte requests per listed edge and round (two marks set, two read, the list read twice and rewritten), 15 000 edges and ~32
-// rounds on a restless heap. Here the list, the edges' endpoints and the marks live in LDS; global memory is touched once per edge, when it
-// takes its colour. The marks are a HASHED table (slot = hash(body), 4 bytes: the priority): two bodies may share a slot, and then an edge is
-// "best" only if it beats the uncoloured edges of every body in its two slots - a stricter test than the rule's, so an edge may take its
-// colour a round later, never earlier: it still takes it after all its higher-priority neighbours and before all lower ones, and the result
-// is the greedy colouring in priority order whatever the rounds were (winners of one round are never adjacent). Every thread owns the edges
-// t, t + 1024, ... and keeps its survivors packed at the front of that column: no list compaction across threads, three barriers per round.
-__global__ void __launch_bounds__(1024) k_col_rounds_lds(uint32_t *info, const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                                                     const uint32_t *__restrict__ flags, uint64_t *used, Counters *cnt,
-                                                     const uint32_t *__restrict__ list, uint32_t cap, uint32_t lds_words, uint32_t max_rounds) {
-    extern __shared__ uint32_t col_lds[];   // em[n0] manifold, es[n0] endpoint slots (slot A | dynamic A << 15 | slot B << 16 | dynamic B << 31), mark[T]
-    __shared__ uint32_t alive[2], left_sum;
-    const uint32_t n0 = cnt->unc_count;
-    if (n0 == 0 || n0 > cap) { if (threadIdx.x == 0) cnt->col_wg_rounds = 0; return; }
-    uint32_t *em = col_lds, *es = col_lds + n0, *mark = col_lds + 2 * n0;
-    uint32_t T = 1024, bits = 10;   // table size: what the workgroup's LDS leaves, at most 2^15 slots, no more than ~16 per edge (it is cleared once)
-    while (T < 32768u && 2 * T <= lds_words - 2 * n0 && T < 16u * n0) { T *= 2; ++bits; }
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < T; i += blockDim.x) mark[i] = 0;
-    uint32_t mine = 0;   // live edges of this thread: em[tid + k * 1024], k < mine (its share of the list, packed at the front of its column)
-    for (uint32_t e = tid; e < n0; e += blockDim.x) {
-        const uint32_t m = list[e], a = bA[m], b = bB[m];
-        const uint32_t sa = (a * 0x9E3779B1u) >> (32u - bits), sb = (b * 0x9E3779B1u) >> (32u - bits);
-        const uint32_t to = tid + mine++ * blockDim.x;
-        em[to] = m;
-        es[to] = sa | (is_dynamic(flags[a]) ? 0x8000u : 0u) | (sb << 16) | (is_dynamic(flags[b]) ? 0x80000000u : 0u);
-    }
-    if (tid < 2) alive[tid] = 0;
-    if (tid == 0) left_sum = 0;
-    __syncthreads();
-    auto ld = [](const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };   // other waves' atomics: not through a stale L1 line
-    auto ld32 = [](const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    uint32_t round = 0;
-    for (; round < max_rounds; ++round) {
-        for (uint32_t k = 0; k < mine; ++k) {                                // phase 1: every slot learns the best uncoloured edge of its bodies
-            const uint32_t e = tid + k * blockDim.x, s = es[e], pr = (uint32_t)edge_prio(em[e]);
-            if (s & 0x8000u) atomicMax(&mark[s & 0x7FFFu], pr);
-            if (s >> 31) atomicMax(&mark[(s >> 16) & 0x7FFFu], pr);
-        }
-        __syncthreads();
-        if (tid == 0) alive[(round + 1) & 1] = 0;
-        // phase 2: an edge that is best in both its slots takes its colour. The winners of a thread are taken four at a time with their loads
-        // issued together - bodies and point count, then the bodies' colour masks: two dependent round trips per batch, where one winner after
-        // the other paid them per edge (a thread owns up to 16 listed edges; winners of a round are never adjacent, so their masks are independent)
-        for (uint32_t k = 0;;) {
-            uint32_t nw = 0, we[4];
-            for (; k < mine && nw < 4u; ++k) {
-                const uint32_t e = tid + k * blockDim.x, s = es[e], pr = (uint32_t)edge_prio(em[e]);
-                if (((s & 0x8000u) && mark[s & 0x7FFFu] != pr) || ((s >> 31) && mark[(s >> 16) & 0x7FFFu] != pr)) continue;
-                we[nw++] = e;
-            }
-            if (nw == 0) break;
-            uint32_t wm[4], ws[4], ia[4], ib[4], in[4];
-            uint64_t busy[4];
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j)
-                if (j < nw) { wm[j] = em[we[j]]; ws[j] = es[we[j]]; ia[j] = bA[wm[j]]; ib[j] = bB[wm[j]]; in[j] = ld32(&info[wm[j]]); }
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j)
-                if (j < nw) busy[j] = ((ws[j] & 0x8000u) ? ld(&used[ia[j]]) : 0ull) | ((ws[j] >> 31) ? ld(&used[ib[j]]) : 0ull);
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j)
-                if (j < nw) {
-                    const uint64_t avail = ~busy[j] & ((1ull << kSerialColour) - 1ull);
-                    const uint32_t c = avail ? (uint32_t)__ffsll((long long)avail) - 1 : kSerialColour;   // nothing free: the serial bucket
-                    info[wm[j]] = (in[j] & 0xFF) | (c << 8);
-                    // its marks go at once (nobody else can equal them: the others in these slots read either this priority or zero and stay)
-                    if (ws[j] & 0x8000u) { atomicOr((unsigned long long *)&used[ia[j]], 1ull << c); mark[ws[j] & 0x7FFFu] = 0; }
-                    if (ws[j] >> 31) { atomicOr((unsigned long long *)&used[ib[j]], 1ull << c); mark[(ws[j] >> 16) & 0x7FFFu] = 0; }
-                    em[we[j]] = 0xFFFFFFFFu;
-                }
-        }
-        __threadfence_block(); __syncthreads();   // the marks have been read; the colours' atomics are at the L2 before the next round reads `used`
-        uint32_t kept = 0;
-        for (uint32_t k = 0; k < mine; ++k) {                                // the survivors clear their slots and move to the front of the column
-            const uint32_t e = tid + k * blockDim.x, m = em[e];
-            if (m == 0xFFFFFFFFu) continue;
-            const uint32_t s = es[e];
-            if (s & 0x8000u) mark[s & 0x7FFFu] = 0;
-            if (s >> 31) mark[(s >> 16) & 0x7FFFu] = 0;
-            const uint32_t to = tid + kept * blockDim.x;
-            if (to != e) { em[to] = m; es[to] = s; }
-            ++kept;
-        }
-        mine = kept;
-        if (__ballot(mine != 0) && (tid & 63u) == 0) alive[round & 1] = 1;
-        __syncthreads();
-        if (!alive[round & 1]) { ++round; break; }
-    }
-    // what max_rounds left over goes to the multi-block rounds (their marks were cleared by k_col_prepare and never touched here)
-    uint32_t left = mine;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) left += __shfl_xor(left, off);
-    if ((tid & 63u) == 0 && left) atomicAdd(&left_sum, left);
-    __syncthreads();
-    if (tid == 0) { cnt->uncoloured = left_sum; cnt->col_wg_rounds = round; }
-}
-__global__ void k_col_best(uint32_t M, const uint32_t *__restrict__ info, const uint32_t *__restrict__ bA,
-                           const uint32_t *__restrict__ bB, const uint32_t *__restrict__ flags, uint64_t *best_cur,
-                           uint64_t *best_next, const Counters *cnt) {
-    if (cnt->uncoloured == 0) return;
-    uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    uint32_t in = info[m];
-    if ((in & 0xFF) == 0 || (in >> 8) != kNoColour) return;
-    uint32_t a = bA[m], b = bB[m];
-    if (edge_asleep(flags[a], flags[b])) return;
-    uint64_t pr = edge_prio(m);
-    if (is_dynamic(flags[a])) { atomicMax((unsigned long long *)&best_cur[a], pr); best_next[a] = 0; }
-    if (is_dynamic(flags[b])) { atomicMax((unsigned long long *)&best_cur[b], pr); best_next[b] = 0; }
-}
-__global__ void k_col_assign(uint32_t M, uint32_t *info, const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                             const uint32_t *__restrict__ flags, const uint64_t *__restrict__ best_cur, uint64_t *used,
-                             Counters *cnt) {
-    if (cnt->uncoloured == 0) return;
-    uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t done = 0;
-    if (m < M) {
-        uint32_t in = info[m];
-        if ((in & 0xFF) != 0 && (in >> 8) == kNoColour) {
-            uint32_t a = bA[m], b = bB[m];
-            bool da = is_dynamic(flags[a]), db = is_dynamic(flags[b]);
-            uint64_t pr = edge_prio(m);
-            if (!edge_asleep(flags[a], flags[b]) && !(da && best_cur[a] != pr) && !(db && best_cur[b] != pr)) {
-                uint64_t busy = (da ? used[a] : 0ull) | (db ? used[b] : 0ull);
-                const uint64_t avail = ~busy & ((1ull << kSerialColour) - 1ull);
-                const uint32_t c = avail ? (uint32_t)__ffsll((long long)avail) - 1 : kSerialColour;   // nothing free: the serial bucket
-                info[m] = (in & 0xFF) | (c << 8);
-                if (da) used[a] |= 1ull << c;
-                if (db) used[b] |= 1ull << c;
-                done = 1;
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) done += __shfl_xor(done, off);
-    if ((threadIdx.x & 63) == 0 && done) atomicSub(&cnt->uncoloured, done);
-}
-DI uint32_t colour_key(uint32_t m, const uint32_t *__restrict__ info, const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                       const uint32_t *__restrict__ flags, bool sleeping) {
-    // within a colour, manifolds are grouped by point count (4 first): the solve kernels then know a lane's point
-    // count from its position alone (no dependent load) and waves are uniform in it
-    uint32_t in = info[m];
-    uint32_t np = in & 0xFF;
-    if (sleeping && np && edge_asleep(flags[bA[m]], flags[bB[m]])) np = 0;   // not part of this step's solve
-    return np ? (((in >> 8) << 2) | (4u - np)) : 0xFFu;
-}
-// Stable counting sort of the manifolds by (colour, point count) key - at most 256 distinct keys. (rocPRIM's radix sort
-// falls back to a merge sort for an 8-bit key range: 1 block-sort + 16 merge launches, ~90 us per step.)
-//  k_cs_hist:    per 1024-element block, the count of every key          -> hist[key * nblocks + block]
-//  scan_u32:     exclusive scan of that key-major table                   -> where each (key, block) run starts
-//  k_cs_scatter: every element's slot = its run's start + its rank among the block's earlier elements with its key
-//  Scenes of up to kCsDirectBlocks blocks (the headline pile: 174) take two launches instead of five (round 5): the
-//  histogram table is block-major there and k_cs_hist<true> also accumulates the key counts of every kCsSuper blocks (`sup`, integer
-//  sums: the same values whatever the order); k_cs_scatter<true> gets the run starts of its block from at most 16 + 15 table rows,
-//  builds the key starts from the totals, and block 0 publishes the colour ranges (k_col_offsets' work). No library scan on the hot path.
-template <bool DIRECT>
-__global__ void __launch_bounds__(kCsBlock) k_cs_hist(uint32_t M, uint32_t *keys, uint32_t *hist, uint32_t nblocks, const uint32_t *__restrict__ info,
-                                                      const uint32_t *__restrict__ bA, const uint32_t *__restrict__ bB,
-                                                      const uint32_t *__restrict__ flags, bool sleeping, uint32_t *sup) {
-    __shared__ uint32_t h[kCsKeys];
-    if (threadIdx.x < kCsKeys) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t m = blockIdx.x * kCsBlock + threadIdx.x;
-    if (m < M) {
-        const uint32_t key = colour_key(m, info, bA, bB, flags, sleeping);
-        keys[m] = key;
-        atomicAdd(&h[key & 0xFFu], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < kCsKeys) {
-        hist[DIRECT ? blockIdx.x * kCsKeys + threadIdx.x : threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
-        if (DIRECT && h[threadIdx.x]) atomicAdd(&sup[(blockIdx.x / kCsSuper) * kCsKeys + threadIdx.x], h[threadIdx.x]);
-    }
-}
-template <bool DIRECT>
-__global__ void __launch_bounds__(kCsBlock) k_cs_scatter(uint32_t M, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ start,
-                                                         uint32_t nblocks, uint32_t *keys_sorted, uint32_t *order, Counters *cnt, const uint32_t *__restrict__ sup) {
-    __shared__ uint32_t base[kCsKeys];
-    if (DIRECT) {   // `start` is the block-major histogram table
-        __shared__ uint32_t wsum[4], part[kCsKeys];
-        uint32_t before = 0, total = 0;
-        {   // lanes 0..255: the super-block rows (key totals; what lies before this block's super-block); lanes 256..511: the rows of
-            // the blocks before this one inside its super-block - at most 16 + 15 independent loads per key
-            const uint32_t k = threadIdx.x & (kCsKeys - 1), q = threadIdx.x >> 8, sb = blockIdx.x / kCsSuper, nsup = (nblocks + kCsSuper - 1) / kCsSuper;
-            if (q == 0) {
-                uint32_t v[kCsDirectBlocks / kCsSuper];
-#pragma unroll
-                for (uint32_t u = 0; u < kCsDirectBlocks / kCsSuper; ++u) v[u] = u < nsup ? sup[u * kCsKeys + k] : 0u;
-#pragma unroll
-                for (uint32_t u = 0; u < kCsDirectBlocks / kCsSuper; ++u) { total += v[u]; before += u < sb ? v[u] : 0u; }
-            } else if (q == 1) {
-                uint32_t v[kCsSuper], inner = 0;
-#pragma unroll
-                for (uint32_t u = 0; u < kCsSuper; ++u) { const uint32_t b = sb * kCsSuper + u; v[u] = b < blockIdx.x ? start[b * kCsKeys + k] : 0u; }
-#pragma unroll
-                for (uint32_t u = 0; u < kCsSuper; ++u) inner += v[u];
-                part[k] = inner;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < kCsKeys) before += part[threadIdx.x];
-        // exclusive scan of the 256 key totals (lanes 0..255 = waves 0..3)
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        uint32_t inc = total;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(inc, d); if ((int)lane >= d) inc += u; }
-        if (wave < 4 && lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        if (threadIdx.x < kCsKeys) {
-            uint32_t key_start = inc - total;
-            for (uint32_t w = 0; w < wave; ++w) key_start += wsum[w];
-            base[threadIdx.x] = key_start + before;
-            if (blockIdx.x == 0 && threadIdx.x < 4 * kMaxContactColours && total) {   // what k_col_offsets reads off the sorted keys
-                cnt->colour_start[threadIdx.x] = key_start; cnt->colour_end[threadIdx.x] = key_start + total;
-            }
-        }
-    } else if (threadIdx.x < kCsKeys) base[threadIdx.x] = start[threadIdx.x * nblocks + blockIdx.x];
-    __syncthreads();
-    const uint32_t m = blockIdx.x * kCsBlock + threadIdx.x;
-    const bool valid = m < M;
-    const uint32_t key = valid ? (keys[m] & 0xFFu) : 0xFFFFFFFFu;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // rank among the lower lanes of this wave with the same key, and the wave's count of that key (at its first lane)
-    uint32_t rank = 0, count = 0;
-    bool first = false;
-    uint64_t todo = __ballot(valid);
-    while (todo) {
-        const uint32_t k = __shfl(key, __ffsll((long long)todo) - 1);
-        const uint64_t same = __ballot(valid && key == k);
-        if (valid && key == k) {
-            rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-            count = (uint32_t)__popcll(same);
-            first = rank == 0;
-        }
-        todo &= ~same;
-    }
-    for (uint32_t w = 0; w < kCsBlock / 64; ++w) {   // waves take their turns in order: keeps the sort stable
-        if (wave == w && valid) {
-            const uint32_t pos = base[key] + rank;
-            keys_sorted[pos] = key; order[pos] = m;
-        }
-        __syncthreads();
-        if (wave == w && valid && first) base[key] += count;
-        __syncthreads();
-    }
-}
-__global__ void k_col_offsets(uint32_t M, const uint32_t *__restrict__ keys_sorted, Counters *cnt) {
-    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= M) return;
-    uint32_t c = keys_sorted[p];
-    if (c >= 4 * kMaxContactColours) return;
-    if (p == 0 || keys_sorted[p - 1] != c) cnt->colour_start[c] = p;
-    if (p == M - 1 || keys_sorted[p + 1] != c) cnt->colour_end[c] = p + 1;
-}
 
 // ------------------------------------------------------------------ row math shared by prep / solve
 struct BRef { f3 pos, org; q4 orn; f3 v, w; float inv_m; m3 inv_I; };   // org: constraint_body::origin - the frame of every pivot (= pos without a centre-of-mass offset)
@@ -2888,7 +2125,7 @@ __global__ void k_pos_writeback(uint32_t n, Bodies b, const float4 *__restrict__
 // first look at the own hand-off slot), then what needs one of those (the body's local inverse inertia through the body index, the
 // island's error of the previous iteration through its label). Round 3's kernel took four levels (key -> order / bodies / next -> the
 // manifold's points and the body record -> poll): its trace showed 3.5 us from "task begins" to "first poll back" against 1.5 us of
-// arithmetic and 1.3 us of waiting per task. Measured and dropped (round 4, scripts/runs/c5-c9.sh): requesting the wave's NEXT task's
+// arithmetic and 1.3 us of waiting per task. Measured and dropped (round 4, DESIGN section 3 "Round 4"): requesting the wave's NEXT task's
 // inputs while the current one runs - before its polls, or at the moment its hand-offs have arrived, with the island's error looked at
 // only after the arithmetic (256 VGPRs): the time to the first poll falls from 2.3 to 1.3 us and the arithmetic section grows by as
 // much; leaving out the scattered point stores (experiment): no difference - a launch is one sweep over 16-18 colours that advances
@@ -3442,181 +2679,6 @@ static void rec(edynhip_ctx *c, int idx) {
     if (c->timer.e && ((c->timer.mask >> idx) & 1u)) (void)hipEventRecord(c->timer.e[idx], c->stream);
 }
 
-int islands(edynhip_ctx *c) {
-    hipStream_t s = c->stream;
-    const uint32_t n = c->b.n, M = c->num_manifolds;
-    if (n == 0) return EDYNHIP_OK;
-    const Manifolds &mf = c->m[c->cur];
-    const bool sleeping = c->sleep_active();   // (a world in which no body can sleep runs no sleep kernels: ctx.hpp num_sleepable)
-    c->island_labels_valid = true;
-    // union-find forest lives in isl_done (scratch until the position solver) to keep b.island stable for readers
-    uint32_t *forest = c->isl_done;
-    c->solve_begin_done = false;
-    const uint32_t force = c->force_islands ? 1u : 0u;
-    const uint32_t pm = c->prev_num_manifolds;
-    c->force_islands = false;
-    // No manifold now or in the previous step, nothing edited, no sleep decisions to take: the labels stand and every kernel below would
-    // return at once - not launched at all (a world of joints only: 4 of its ~20 launches per step)
-    if (!force && M == 0 && pm == 0 && !sleeping && c->full_step) return EDYNHIP_OK;
-    // An in-place step (broadphase.hip: the pair set is last step's) has nothing to relabel. Otherwise the counters fetched with
-    // the pair count say whether every certificate manifold is still there (see CC_INCREMENTAL above).
-    const bool inplace = c->inplace_step;
-    c->inplace_step = false;
-    const int mode = force ? CC_FULL : inplace ? CC_SKIP
-                     : (c->full_step && c->cnt_host->tree_found == c->cnt_host->tree_total) ? CC_INCREMENTAL : CC_FULL;
-    (void)pm;
-    if (mode == CC_FULL) ++c->cc_full_steps; else if (mode == CC_INCREMENTAL) ++c->cc_incremental_steps;
-    // island sleeping: last step's labels, before the hooks rewrite them (the merge rule of k_sleep_sizes / k_sleep_carry reads them)
-    if (sleeping && mode != CC_SKIP && c->sleep_old_label)
-        EH_HIP(c, hipMemcpyAsync(c->sleep_old_label, c->b.island, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    // the solve's per-body start rides on the flatten kernel when nothing in between looks at velocities or sleep flags
-    const bool begin = c->full_step && !sleeping && !c->has_restitution;
-    auto flatten = [&](uint32_t *forest_or_labels) {
-        uint32_t *split = (sleeping && mode == CC_FULL) ? c->sleep_state : nullptr;
-        if (begin) hipLaunchKernelGGL(k_cc_flatten<true>, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b.flags, forest_or_labels, c->b.island, c->cnt, mode, c->b, c->cfg.fixed_dt, c->rows.first_slot, split);
-        else hipLaunchKernelGGL(k_cc_flatten<false>, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b.flags, forest_or_labels, c->b.island, c->cnt, mode, c->b, c->cfg.fixed_dt, c->rows.first_slot, split);
-        c->solve_begin_done = begin;
-    };
-    if (mode == CC_FULL) {
-        hipLaunchKernelGGL(k_cc_init, dim3(blocks(n, 256)), dim3(256), 0, s, n, forest, c->cnt, mf, M, c->b.flags);
-        if (c->j.n) hipLaunchKernelGGL(k_cc_hook, dim3(blocks(c->j.n, 256)), dim3(256), 0, s, c->j.n, c->j.bodyA, c->j.bodyB, c->b.flags, forest);
-        static const int compress_env = getenv("EDYNHIP_CC_COMPRESS") ? atoi(getenv("EDYNHIP_CC_COMPRESS")) : 1;   // developer knob: passes of k_cc_compress
-        if (M) for (int pass = 0; pass < compress_env; ++pass) hipLaunchKernelGGL(k_cc_compress, dim3(blocks(n, 256)), dim3(256), 0, s, n, forest, c->b.flags);
-        // (round 5, measured and dropped: one lane per EDGE on the compressed forest instead of the per-body walks - 2 x 67 us against 57:
-        //  what costs is not the depth of the finds any more but the unions themselves, thousands of trees hooking into one root)
-        if (M) hipLaunchKernelGGL(k_cc_hook_bodies, dim3(blocks(n, 256)), dim3(256), 0, s, n, mf, M, c->b.flags, forest, c->cnt);
-        flatten(forest);
-    } else if (mode == CC_INCREMENTAL) {   // the labels themselves are the forest (roots = lowest index: depth 1)
-        hipLaunchKernelGGL(k_cc_hook_new, dim3(32), dim3(256), 0, s, c->new_edges, c->new_edge_m, mf.tree, c->b.flags, c->b.island, c->cnt);
-        flatten(c->b.island);
-    }
-    if (sleeping) {
-        const bool relabelled = mode != CC_SKIP && c->sleep_old_label != nullptr;
-        SleepMerge sm{c->sleep_old_label, c->sleep_prev_n, c->sleep_size, c->sleep_best, c->sleep_carried};
-        if (!relabelled) sm.best = nullptr;
-        if (relabelled) hipLaunchKernelGGL(k_sleep_sizes, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, mf, M, c->j, sm);
-        hipLaunchKernelGGL(k_sleep_scan, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, c->sleep_state, sm);
-        if (relabelled) hipLaunchKernelGGL(k_sleep_carry, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, sm, c->sleep_since);
-        c->sleep_prev_n = n;
-        hipLaunchKernelGGL(k_sleep_edges, dim3(32), dim3(256), 0, s, c->new_edges, c->cnt, c->b.island, c->sleep_state);
-        hipLaunchKernelGGL(k_sleep_decide, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, c->sleep_state, c->sleep_action, c->sleep_since, c->sim_clock,
-                           relabelled ? c->sleep_carried : (const double *)nullptr);
-        hipLaunchKernelGGL(k_sleep_apply, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, c->sleep_action, c->cnt);
-    }
-    EH_HIP(c, hipGetLastError());
-    return EDYNHIP_OK;
-}
-
-// `between`: called once, after the steady-state colouring and its counter publish are enqueued and before the host waits for the
-// counters - what it enqueues runs while the answer travels (it must not depend on the answer). *first_final tells the caller whether
-// the counters of that first publish were the final ones (no multi-block colouring rounds, no second sort).
-template <typename Between>
-static int colour_contacts(edynhip_ctx *c, Between between, bool *first_final) {
-    *first_final = false;
-    hipStream_t s = c->stream;
-    const uint32_t M = c->num_manifolds, n = c->b.n;
-    Manifolds &mf = c->m[c->cur];
-    c->num_active = 0;
-    if (M == 0) { c->num_colours = 0; return EDYNHIP_OK; }
-    if (!c->full_step) {   // inside edynhip_step: `used` was cleared by the previous k_finish, the counters by k_step_reset
-        EH_HIP(c, hipMemsetAsync(c->used, 0, (size_t)n * sizeof(uint64_t), s));
-        EH_HIP(c, hipMemsetAsync(c->isl_top, 0, (size_t)n * sizeof(uint2), s));
-        EH_HIP(c, hipMemsetAsync(&c->cnt->uncoloured, 0, 2 * sizeof(uint32_t), s));   // uncoloured, colour_overflow
-        EH_HIP(c, hipMemsetAsync(c->cnt->colour_start, 0, 8 * kMaxColours * sizeof(uint32_t), s));
-    }
-    hipLaunchKernelGGL(k_col_tops, dim3(blocks(M, 1024)), dim3(1024), 0, s, M, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->b.island, c->isl_top, c->cs_sup);
-    hipLaunchKernelGGL(k_col_prepare, dim3(blocks(M, 1024)), dim3(1024), 0, s, M, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->used, c->best[0], c->best[1], c->cnt, c->b.island, c->isl_top, c->col_unc);
-    uint32_t round = 0, total_rounds = 0;
-    auto run_rounds = [&](uint32_t count) {
-        for (uint32_t r = 0; r < count; ++r, ++round) {
-            uint64_t *bc = c->best[round & 1], *bn = c->best[(round + 1) & 1];
-            hipLaunchKernelGGL(k_col_best, dim3(blocks(M, 256)), dim3(256), 0, s, M, mf.info, mf.bodyA, mf.bodyB, c->b.flags, bc, bn, c->cnt);
-            hipLaunchKernelGGL(k_col_assign, dim3(blocks(M, 256)), dim3(256), 0, s, M, mf.info, mf.bodyA, mf.bodyB, c->b.flags, bc, c->used, c->cnt);
-        }
-        total_rounds += count;
-    };
-    bool first = true;
-    auto sort_and_fetch = [&]() -> int {
-        {
-            const uint32_t nb = blocks(M, kCsBlock);
-            static const bool direct_env = !(getenv("EDYNHIP_DIRECT_SORT") && getenv("EDYNHIP_DIRECT_SORT")[0] == '0');   // developer knob (A/B)
-            if (nb <= kCsDirectBlocks && direct_env) {
-                if (!first) EH_HIP(c, hipMemsetAsync(c->cs_sup, 0, (size_t)(kCsDirectBlocks / kCsSuper) * kCsKeys * sizeof(uint32_t), s));   // (the step's first sort: cleared by k_col_tops)
-                hipLaunchKernelGGL(k_cs_hist<true>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_hist, nb, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->sleeping, c->cs_sup);
-                hipLaunchKernelGGL(k_cs_scatter<true>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_hist, nb, c->col_keys_sorted, c->rows.order, c->cnt, c->cs_sup);
-            } else {
-                hipLaunchKernelGGL(k_cs_hist<false>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_hist, nb, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->sleeping, (uint32_t *)nullptr);
-                EH_TRY(scan_u32(c, c->cs_hist, c->cs_start, kCsKeys * nb));
-                hipLaunchKernelGGL(k_cs_scatter<false>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_start, nb, c->col_keys_sorted, c->rows.order, c->cnt, (const uint32_t *)nullptr);
-                hipLaunchKernelGGL(k_col_offsets, dim3(blocks(M, 256)), dim3(256), 0, s, M, c->col_keys_sorted, c->cnt);
-            }
-        }
-        uint32_t ticket = 0;
-        EH_TRY(publish_counters(c, sizeof(Counters), &ticket));
-        if (first) between();
-        first = false;
-        EH_TRY(wait_counters(c, ticket));
-        return EDYNHIP_OK;
-    };
-    // Steady state: the few new edges are coloured by one workgroup (k_col_rounds) and ONE fetch brings the offsets; what it
-    // could not finish (a long list, or more rounds than it runs) is left to the multi-block rounds below.
-    static const bool col_lds_env = getenv("EDYNHIP_COL_LDS") && getenv("EDYNHIP_COL_LDS")[0] == '1';   // developer knob (A/B): the rounds with their marks in a hashed LDS table (k_col_rounds)
-    constexpr uint32_t kColMinTable = 8192;   // mark slots the longest list still leaves room for
-    if (c->col_lds_edges == 0) {   // the listed edges and the mark table live in LDS: as much as one workgroup may have (8 bytes per edge + 4 per slot)
-        int max_lds = 0;
-        (void)hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device);
-        uint32_t bytes = max_lds > 65536 ? (uint32_t)max_lds - 1024u : 48u * 1024u;
-        const void *fn = col_lds_env ? (const void *)k_col_rounds_lds : (const void *)k_col_rounds;
-        if (bytes > 48u * 1024u && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            bytes = 48u * 1024u;
-        }
-        c->col_lds_bytes = bytes;
-        c->col_lds_edges = std::min<uint32_t>(kColUncCap, (bytes - (col_lds_env ? 4u * kColMinTable : 0u)) / 8u);
-    }
-    if (col_lds_env)
-        hipLaunchKernelGGL(k_col_rounds_lds, dim3(1), dim3(1024), (size_t)c->col_lds_bytes, s, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->used, c->cnt,
-                           c->col_unc, c->col_lds_edges, c->col_lds_bytes / 4u, 256u);
-    else
-        hipLaunchKernelGGL(k_col_rounds, dim3(1), dim3(1024), (size_t)c->col_lds_edges * 8u, s, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->best[0], c->best[1], c->used, c->cnt,
-                           c->col_unc, c->col_lds_edges, 256u);
-    EH_TRY(sort_and_fetch());
-    *first_final = c->cnt_host->uncoloured == 0;
-    if (c->cnt_host->uncoloured != 0) {
-        uint32_t batch = 4;
-        while (c->cnt_host->uncoloured != 0) {
-            if (c->cnt_host->colour_overflow) break;
-            run_rounds(batch);
-            if (batch < 64) batch *= 2;   // a scene coloured from scratch needs hundreds of rounds; steady state needs none
-            EH_TRY(fetch_counters(c, 8 * sizeof(uint32_t)));
-            if (total_rounds > 65536) return set_error(c, EDYNHIP_ERR_COLOURS, "colouring did not converge");
-        }
-        EH_HIP(c, hipMemsetAsync(c->cnt->colour_start, 0, 8 * kMaxColours * sizeof(uint32_t), s));
-        EH_TRY(sort_and_fetch());
-    }
-    // (no contact count is an error any more: what does not fit the 62 parallel colours goes to the serial bucket, ctx.hpp)
-    c->stats.colour_rounds = total_rounds + c->cnt_host->col_wg_rounds;
-    uint32_t nc = 0, na = 0;
-    for (uint32_t k = 0; k < kMaxColours; ++k) {
-        uint32_t begin = 0xFFFFFFFFu, pos = 0, cnt4[4];
-        for (uint32_t g = 0; g < 4; ++g) {
-            const uint32_t a = c->cnt_host->colour_start[4 * k + g], e = c->cnt_host->colour_end[4 * k + g];
-            cnt4[g] = e - a;
-            if (e > a && a < begin) begin = a;
-        }
-        if (begin == 0xFFFFFFFFu) { c->colour_start[k] = c->colour_end[k] = 0; continue; }
-        c->colour_start[k] = begin;
-        pos = begin;
-        for (uint32_t g = 0; g < 3; ++g) { pos += cnt4[g]; c->colour_split[k][g] = pos; }
-        c->colour_end[k] = pos + cnt4[3];
-        nc = k + 1;
-        na = c->colour_end[k] > na ? c->colour_end[k] : na;
-    }
-    c->num_colours = nc;
-    c->num_active = na;
-    return EDYNHIP_OK;
-}
-
 // Kernel instantiations by (warm start, push hand-offs) and the context's contact arithmetic (ctx.hpp Arith: the reference's operations
 // by default, EDYNHIP_FLAG_FUSED_VELOCITY_ROWS / EDYNHIP_FLAG_BLOCK_POSITION opt in to the coloured order's own forms).
 using ContactSolveFn = void (*)(uint32_t, uint32_t, Split, const uint32_t *, const uint32_t *, float4 *, uint32_t, float4 *, const float *, float4 *);
@@ -3643,84 +2705,81 @@ static const void *df_velocity_fn(uint32_t lanes, bool fused) {
 }
 static const void *df_position_fn(bool block) { return block ? (const void *)k_pos_contacts_df<true> : (const void *)k_pos_contacts_df<false>; }
 
-int solve(edynhip_ctx *c) {
-    hipStream_t s = c->stream;
-    const bool fused_rows = (c->cfg.flags & EDYNHIP_FLAG_FUSED_VELOCITY_ROWS) != 0, block_pos = (c->cfg.flags & EDYNHIP_FLAG_BLOCK_POSITION) != 0;
-    const uint32_t n = c->b.n;
-    if (n == 0) return EDYNHIP_OK;
-    Manifolds &mf = c->m[c->cur];
-    const float dt = c->cfg.fixed_dt;
-    const uint32_t rcap = mf.cap;
-    rec(c, 3);
-    EH_TRY(restitution(c));   // solve_restitution comes first in solver::update (solver.cpp:397); a no-op without bouncy materials
-    // gravity / zeroed deltas do not depend on the colouring: enqueued first, they run while the host waits for the counters
-    if (!c->solve_begin_done) hipLaunchKernelGGL(k_solve_begin, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, dt, c->rows.first_slot);
-    c->solve_begin_done = false;
-    // Contact-only scenes: the whole velocity solve as one dataflow launch (see k_contact_solve_df).
-    if (c->df_mode < 0) {
-        c->df_mode = 0;
-        const char *env = getenv("EDYNHIP_DATAFLOW");
-        int per_cu = 0, ncu = 0, coop = 0;
-        if (!(env && env[0] == '0') &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, df_velocity_fn(1u, fused_rows), kDfBlock, 0) == hipSuccess &&
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess &&
-            hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && per_cu > 0 && ncu > 0 && coop) {
-            c->df_lanes = (uint32_t)per_cu * (uint32_t)ncu;   // resident waves (one per workgroup)
-            int per_cu2 = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, df_velocity_fn(2u, fused_rows), 64, 0) == hipSuccess && per_cu2 > 0)
-                c->df2_waves = (uint32_t)per_cu2 * (uint32_t)ncu;
-            int per_cu4 = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, df_velocity_fn(4u, fused_rows), 64, 0) == hipSuccess && per_cu4 > 0)
-                c->df4_waves = (uint32_t)per_cu4 * (uint32_t)ncu;
-            int per_cu_p = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_p, df_position_fn(block_pos), 64, 0) == hipSuccess && per_cu_p > 0)
-                c->dfp_waves = (uint32_t)per_cu_p * (uint32_t)ncu;
-            c->df_mode = 1;
-        }
-        (void)hipGetLastError();
+// One-time occupancy probe of a context (df_mode < 0): how many waves of each dataflow kernel the device holds at once. Leaves df_mode
+// at 1 when the dataflow schedules can be used (EDYNHIP_DATAFLOW=0 or a device without cooperative launches: 0).
+static void probe_dataflow(edynhip_ctx *c, bool fused_rows, bool block_pos) {
+    c->df_mode = 0;
+    int per_cu = 0, ncu = 0, coop = 0;
+    if (c->knobs.dataflow &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, df_velocity_fn(1u, fused_rows), kDfBlock, 0) == hipSuccess &&
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess &&
+        hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && per_cu > 0 && ncu > 0 && coop) {
+        c->df_lanes = (uint32_t)per_cu * (uint32_t)ncu;   // resident waves (one per workgroup)
+        int per_cu2 = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, df_velocity_fn(2u, fused_rows), 64, 0) == hipSuccess && per_cu2 > 0)
+            c->df2_waves = (uint32_t)per_cu2 * (uint32_t)ncu;
+        int per_cu4 = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, df_velocity_fn(4u, fused_rows), 64, 0) == hipSuccess && per_cu4 > 0)
+            c->df4_waves = (uint32_t)per_cu4 * (uint32_t)ncu;
+        int per_cu_p = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_p, df_position_fn(block_pos), 64, 0) == hipSuccess && per_cu_p > 0)
+            c->dfp_waves = (uint32_t)per_cu_p * (uint32_t)ncu;
+        c->df_mode = 1;
     }
+    (void)hipGetLastError();
+}
+
+// What one step's solve launches, decided by plan_solve from the context, its knobs and the counters the colouring fetched. Two things
+// can still change it while the step is enqueued, both only towards the per-colour launches: this step's island sizes (confirm_islands)
+// and a resident launch that the runtime refuses (launch_velocity, launch_position).
+struct SolvePlan {
+    bool fused_rows = false, block_pos = false;   // the context's contact arithmetic (ctx.hpp Arith)
+    uint32_t na = 0;                // active manifolds
+    bool serial = false;            // the serial bucket (ctx.hpp kSerialColour) is not empty
+    uint32_t nc_par = 0;            // colours solved in parallel
+    uint32_t first_tail = 0;        // colours [first_tail, nc_par) each fit one workgroup and share one launch ...
+    TailRanges tail{};              // ... over these ranges
+    bool isl_candidate = false;     // the constraints are bucketed by island (joints or contact_extras rows, no serial bucket)
+    uint32_t largest = 0xFFFFFFFFu; // largest island of the previous step's bucketing, in constraints (~0: not known)
+    bool mixed = false;             // islands with joints on the island-fused kernels, the others on the dataflow launch
+    bool isl_fused = false;         // every island on the island-fused kernels
+    bool push = false;              // the contact sweeps hand the body deltas on through the slots (Rows::dslot)
+    uint32_t lanes = 0, vel_grid = 0;   // dataflow velocity launch: lanes per manifold (0: no such launch) and workgroups
+    bool pos_df = false;            // dataflow position launches ...
+    uint32_t pos_grid = 0;          // ... of this many workgroups
+    void set_largest(uint32_t items) { largest = items; isl_fused = isl_candidate && !mixed && largest <= kIslFusedLimit; }
+    void drop_dataflow() { lanes = 0; pos_df = false; }
+    const uint8_t *df_skip(const edynhip_ctx *c) const { return mixed ? c->rows.skip : nullptr; }
+    uint32_t schedule(uint32_t num_joints) const {   // edynhip_stats::solve_schedule, once the velocity solve is enqueued
+        return (na + num_joints) == 0 ? EDYNHIP_SCHEDULE_NONE
+               : lanes ? (mixed ? EDYNHIP_SCHEDULE_MIXED : lanes == 4u ? EDYNHIP_SCHEDULE_DATAFLOW4 : lanes == 2u ? EDYNHIP_SCHEDULE_DATAFLOW2 : EDYNHIP_SCHEDULE_DATAFLOW1)
+               : isl_fused ? EDYNHIP_SCHEDULE_ISLAND_FUSED : EDYNHIP_SCHEDULE_PER_COLOUR;
+    }
+};
+constexpr bool kPwInPrep = true;   // k_prep_contacts also writes the position solve's lane-indexed copy of the points (Rows::pw) on the push schedules
+constexpr uint32_t kMixedMinFree = 1024;   // manifolds outside jointed islands that make the dataflow launch worth its fixed cost
+constexpr uint32_t kIslGrid = 4096;   // one wave each; a block takes islands blockIdx.x, + kIslGrid, ...
+
+static SolvePlan plan_solve(const edynhip_ctx *c) {
+    const Knobs &kn = c->knobs;
     const Joints &j = c->j;
-    // Contact-only worlds on the dataflow schedule: the row preparation does not wait for the host to read the colouring's counters.
-    // It is enqueued right behind the counter publish over ALL manifolds - the active ones are the prefix of the sorted order whose
-    // keys name a colour (k_prep_contacts by_key) - and runs while the answer travels to the host and the next launches travel back
-    // (14 us of idle GPU per step on the headline pile, profiles/r04_timeline_pile32k.txt). If the colouring turns out unfinished
-    // (uncoloured edges left for the multi-block rounds: a scene coloured from scratch) the rows are prepared again after the second sort;
-    // a non-empty serial bucket only drops `push` - the slot table written for it is read through the bodies' colour masks alone.
-    static const bool spec_env = !(getenv("EDYNHIP_SPECULATE") && getenv("EDYNHIP_SPECULATE")[0] == '0');
-    const bool kPwInPrep = true;   // k_prep_contacts also writes the position solve's lane-indexed copy of the points (Rows::pw) on the push schedules
-    bool spec_prep = false;
-    auto speculative_prep = [&]() {
-        rec(c, 4);
-        if (!(spec_env && j.n == 0 && !c->extras && c->df_mode == 1 && c->full_step && c->num_manifolds > 0)) return;
-        const uint32_t M = c->num_manifolds;
-        hipLaunchKernelGGL(k_prep_contacts<false>, dim3(blocks(M, 128)), dim3(128), 0, s, M, c->rows, rcap, mf, c->b, dt, c->col_keys_sorted, true, true, kPwInPrep);
-        spec_prep = true;
-    };
-    bool first_final = false;
-    EH_TRY(colour_contacts(c, speculative_prep, &first_final));
-    if (!first_final) spec_prep = false;   // the sorted order changed after the speculative launch: prepare again
-    // colour_contacts fetched the counters: with island sleeping, remember whether anything is still awake
-    c->all_asleep = c->sleep_active() && c->full_step && c->num_manifolds > 0 && c->cnt_host->num_awake == 0;
-    if (c->num_manifolds == 0) rec(c, 4);
-    const uint32_t na = c->num_active, nc = c->num_colours;
-    if (j.n) hipLaunchKernelGGL(k_prep_joints, dim3(blocks(j.n, 128)), dim3(128), 0, s, j, c->b, dt, c->isl_joint);
-    if (j.n && c->has_generic) hipLaunchKernelGGL(k_prep_generic, dim3(blocks(j.n, 64)), dim3(64), 0, s, j, c->b, dt);
+    SolvePlan p;
+    p.fused_rows = (c->cfg.flags & EDYNHIP_FLAG_FUSED_VELOCITY_ROWS) != 0;
+    p.block_pos = (c->cfg.flags & EDYNHIP_FLAG_BLOCK_POSITION) != 0;
+    const uint32_t na = p.na = c->num_active, nc = c->num_colours;
     // without joints every delta hand-off stays inside the contact sweeps; contact_extras rows exist on the per-colour schedule only
     // a non-empty serial bucket (a body with more than 62 coloured contacts) also needs the per-colour schedule
-    const bool serial = nc == kSerialColour + 1 && c->colour_end[kSerialColour] > c->colour_start[kSerialColour];
-    const uint32_t nc_par = serial ? kSerialColour : nc;   // colours solved in parallel
+    p.serial = nc == kSerialColour + 1 && c->colour_end[kSerialColour] > c->colour_start[kSerialColour];
+    p.nc_par = p.serial ? kSerialColour : nc;
     // Schedules. Contact-only scene: one dataflow launch (push hand-offs). With joints (or contact_extras rows): the constraints are
     // bucketed by island every step, and the statistics of the PREVIOUS step's bucketing (they arrive with the counters this step
     // fetched anyway) choose: "mixed" - islands with joints go to the island-fused kernels, the (many) manifolds of islands without
     // joints stay on the dataflow launch: a pile next to a rag doll keeps its fast path; "fused" - every island is small: one wave per
     // island; else one launch per colour.
-    static const bool isl_env = !(getenv("EDYNHIP_ISLAND_FUSED") && getenv("EDYNHIP_ISLAND_FUSED")[0] == '0');
-    static const bool mixed_env = !(getenv("EDYNHIP_MIXED") && getenv("EDYNHIP_MIXED")[0] == '0');
-    const IslLists isl{c->isl_cnt, c->isl_off, c->isl_list, c->isl_items, c->isl_sorted, c->isl_joint};
     const bool contacts_only = j.n == 0 && !c->extras;
-    const bool isl_candidate = isl_env && !contacts_only && !serial && (na + j.n) > 0 && (size_t)na + j.n < kIslIdMask;
+    p.isl_candidate = kn.island_fused && !contacts_only && !p.serial && (na + j.n) > 0 && (size_t)na + j.n < kIslIdMask;
     uint32_t largest = 0xFFFFFFFFu, largest_jointed = 0xFFFFFFFFu, free_manifolds = 0;
-    if (isl_candidate) {
+    if (p.isl_candidate) {
         const bool fetched = c->last_fetch_step == c->step_index;   // this step's counters were read after the previous step's fill
         if (fetched && c->isl_prep_step + 1 == c->step_index) {
             largest = c->cnt_host->isl_max_items; largest_jointed = c->cnt_host->isl_max_jitems; free_manifolds = c->cnt_host->isl_free;
@@ -3728,117 +2787,27 @@ int solve(edynhip_ctx *c) {
             largest = c->isl_cache_max; largest_jointed = c->isl_cache_jmax; free_manifolds = c->isl_cache_free;
         }
     }
-    constexpr uint32_t kMixedMinFree = 1024;   // manifolds outside jointed islands that make the dataflow launch worth its fixed cost
-    bool mixed = isl_candidate && mixed_env && j.n > 0 && !c->extras && na > 0 && c->df_mode == 1 && c->cfg.num_position_iterations <= kMaxDfPosIters &&
-                       free_manifolds >= kMixedMinFree && largest_jointed <= kIslFusedLimit && !c->b.com;
-    bool push = na > 0 && !serial && (contacts_only || mixed);
-    if (na) {
-        if (c->extras) hipLaunchKernelGGL(k_prep_contacts<true>, dim3(blocks(na, 128)), dim3(128), 0, s, na, c->rows, rcap, mf, c->b, dt, c->col_keys_sorted, push, false, false);
-        else if (!spec_prep) hipLaunchKernelGGL(k_prep_contacts<false>, dim3(blocks(na, 128)), dim3(128), 0, s, na, c->rows, rcap, mf, c->b, dt, c->col_keys_sorted, push, false, kPwInPrep);
-    }
-    bool isl_fused = false;
-    if (isl_candidate) {
-        JointColours jc{};
-        jc.n = j.num_colours;
-        for (uint32_t k = 0; k <= j.num_colours && k <= kMaxColours; ++k) jc.start[k] = j.colour_start[k];
-        // A world of joints only (no contact this step, no sleeping) whose bodies and joints have not been edited since the lists were
-        // built has the same islands and the same lists: they are kept (chains16k: 4 launches of 28 per step)
-        const bool keep_lists = na == 0 && !c->sleep_active() && c->isl_lists_epoch == c->topology_epoch;
-        if (!keep_lists) {
-        EH_HIP(c, hipMemsetAsync(&c->cnt->isl_num, 0, 4 * sizeof(uint32_t), s));   // isl_num, isl_max_items, isl_max_jitems, isl_free
-        hipLaunchKernelGGL(k_isl_count, dim3(blocks(j.n + na, 256)), dim3(256), 0, s, j.n, na, j, c->rows, c->b, isl);
-        EH_TRY(scan_u32(c, c->isl_cnt, c->isl_off, n + 1));
-        hipLaunchKernelGGL(k_isl_fill, dim3(blocks(j.n + na, 256)), dim3(256), 0, s, j.n, na, j, jc, c->rows, c->col_keys_sorted, c->b, isl, c->cnt);
-        c->isl_lists_epoch = (na == 0 && !c->sleep_active()) ? c->topology_epoch : 0xFFFFFFFFu;
-        }
-        if (largest == 0xFFFFFFFFu && c->last_fetch_step != c->step_index) {
-            // no contacts and nothing with a shape: the step reads no counters at all and the islands are those of the
-            // joints, fixed until the scene is edited - read this step's values once and keep them
-            EH_TRY(fetch_counters(c, sizeof(Counters) - sizeof(uint32_t) * 8 * kMaxColours));
-            largest = c->isl_cache_max = c->cnt_host->isl_max_items;
-            c->isl_cache_jmax = c->cnt_host->isl_max_jitems; c->isl_cache_free = c->cnt_host->isl_free;
-            c->isl_cache_epoch = c->topology_epoch;
-        }
-        c->isl_prep_step = c->step_index;
-        isl_fused = !mixed && largest <= kIslFusedLimit;
-        // The decision above came from the PREVIOUS step's islands. Islands can merge in one step (a rag doll falls onto the pile), and
-        // a wave that finds itself with a 100 000-constraint island would need a large fraction of a second for it: confirm with this
-        // step's sizes (one more counter fetch, ~15 us, only on the fused / mixed schedules and only when the lists were rebuilt)
-        if ((isl_fused || mixed) && !keep_lists) {
-            EH_TRY(fetch_counters(c, sizeof(Counters) - sizeof(uint32_t) * 8 * kMaxColours));
-            if (isl_fused && c->cnt_host->isl_max_items > kIslFusedLimit) isl_fused = false;
-            if (mixed && c->cnt_host->isl_max_jitems > kIslFusedLimit) {   // the jointed islands outgrew the fused kernels: the whole step per colour
-                mixed = false; push = false;
-                if (na) hipLaunchKernelGGL(k_prep_contacts<false>, dim3(blocks(na, 128)), dim3(128), 0, s, na, c->rows, rcap, mf, c->b, dt, c->col_keys_sorted, false, false, false);
-            }
-        }
-    }
-    if (push) {
-        hipLaunchKernelGGL(k_push_links, dim3(blocks(na, 256)), dim3(256), 0, s, na, c->rows, c->col_keys_sorted, c->b, c->used, mixed ? c->isl_joint : nullptr);
-    }
-    const uint8_t *df_skip = mixed ? c->rows.skip : nullptr;
-    IslSolveArgs isl_args{isl, c->cnt, j, c->b, c->rows, mf, rcap, c->extras ? c->rows.rwx : nullptr, 0u, c->isl_err, c->isl_done, mixed ? 1u : 0u};
-    constexpr uint32_t kIslGrid = 4096;   // one wave each; a block takes islands blockIdx.x, + kIslGrid, ...
-    rec(c, 5);
-    uint32_t launches = 0;
-    auto joints_pass = [&](bool warm) {
-        for (uint32_t k = 0; k < j.num_colours; ++k) {
-            uint32_t a = j.colour_start[k], e = j.colour_start[k + 1];
-            if (e <= a) continue;
-            if (warm) hipLaunchKernelGGL(k_joint_solve<true>, dim3(blocks(e - a, 128)), dim3(128), 0, s, a, e, j, c->b);
-            else hipLaunchKernelGGL(k_joint_solve<false>, dim3(blocks(e - a, 128)), dim3(128), 0, s, a, e, j, c->b);
-            ++launches;
-        }
-    };
+    p.mixed = p.isl_candidate && kn.mixed && j.n > 0 && !c->extras && na > 0 && c->df_mode == 1 && c->cfg.num_position_iterations <= kMaxDfPosIters &&
+              free_manifolds >= kMixedMinFree && largest_jointed <= kIslFusedLimit && !c->b.com;
+    p.set_largest(largest);
+    p.push = na > 0 && !p.serial && (contacts_only || p.mixed);
     // maximal suffix of colours that each fit one workgroup -> one launch for all of them
-    TailRanges tail{};
-    uint32_t first_tail = nc_par;
-    while (first_tail > 0 && c->colour_end[first_tail - 1] - c->colour_start[first_tail - 1] <= kTailMax) --first_tail;
-    if (nc_par - first_tail >= 2) {
-        for (uint32_t k = first_tail; k < nc_par; ++k)
+    p.first_tail = p.nc_par;
+    while (p.first_tail > 0 && c->colour_end[p.first_tail - 1] - c->colour_start[p.first_tail - 1] <= kTailMax) --p.first_tail;
+    if (p.nc_par - p.first_tail >= 2) {
+        for (uint32_t k = p.first_tail; k < p.nc_par; ++k)
             if (c->colour_end[k] > c->colour_start[k]) {
-                tail.start[tail.n] = c->colour_start[k]; tail.end[tail.n] = c->colour_end[k];
-                tail.split[tail.n] = Split{c->colour_split[k][0], c->colour_split[k][1], c->colour_split[k][2]};
-                ++tail.n;
+                p.tail.start[p.tail.n] = c->colour_start[k]; p.tail.end[p.tail.n] = c->colour_end[k];
+                p.tail.split[p.tail.n] = Split{c->colour_split[k][0], c->colour_split[k][1], c->colour_split[k][2]};
+                ++p.tail.n;
             }
-    } else first_tail = nc_par;
-    auto contacts_pass = [&](bool warm) {
-        for (uint32_t k = 0; k < first_tail; ++k) {
-            uint32_t a = c->colour_start[k], e = c->colour_end[k];
-            if (e <= a) continue;
-            const Rows &r = c->rows;
-            const Split sp{c->colour_split[k][0], c->colour_split[k][1], c->colour_split[k][2]};
-            const dim3 g(blocks(e - a, 64)), bl(64);
-            if (push) hipLaunchKernelGGL(contact_solve_fn(warm, true, fused_rows), g, bl, 0, s, a, e, sp, (const uint32_t *)r.next, (const uint32_t *)nullptr, r.rw, rcap, r.dslot, (const float *)r.im, (float4 *)nullptr);
-            else hipLaunchKernelGGL(contact_solve_fn(warm, false, fused_rows), g, bl, 0, s, a, e, sp, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, (const float *)nullptr, c->extras ? r.rwx : (float4 *)nullptr);
-            ++launches;
-        }
-        if (tail.n) {
-            const Rows &r = c->rows;
-            const dim3 g(1), bl(kTailThreads);
-            if (push) hipLaunchKernelGGL(contact_tail_fn(warm, true, fused_rows), g, bl, 0, s, tail, (const uint32_t *)r.next, (const uint32_t *)nullptr, r.rw, rcap, r.dslot, (const float *)r.im, (float4 *)nullptr);
-            else hipLaunchKernelGGL(contact_tail_fn(warm, false, fused_rows), g, bl, 0, s, tail, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, (const float *)nullptr, c->extras ? r.rwx : (float4 *)nullptr);
-            ++launches;
-        }
-        if (serial) {
-            const Rows &r = c->rows;
-            const uint32_t a = c->colour_start[kSerialColour], e = c->colour_end[kSerialColour];
-            const Split sp{c->colour_split[kSerialColour][0], c->colour_split[kSerialColour][1], c->colour_split[kSerialColour][2]};
-            hipLaunchKernelGGL(contact_serial_fn(warm, fused_rows), dim3(1), dim3(64), 0, s, a, e, sp, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, c->extras ? r.rwx : (float4 *)nullptr);
-            ++launches;
-        }
-    };
-    bool df_velocity = false, df_two_lane = false, df_four_lane = false;
-    if (push && c->df_mode == 1) {
-        const Rows &r = c->rows;
+    } else p.first_tail = p.nc_par;
+    if (p.push && c->df_mode == 1) {
         // Two lanes per manifold (k_contact_solve_df2) unless disabled; resident waves (measured on MI355X): enough for
         // ~4-5 tasks per wave and sweep while the sweep is latency-bound - more only add polling traffic - and up to every
         // resident slot once the row stream dominates (many islands, millions of points).
         // Lanes per manifold: 4 (k_contact_solve_df4: shortest hop; the default while the sweep is latency-bound), 2 (k_contact_solve_df2)
         // or 1 (k_contact_solve_df: least row traffic, for bandwidth-bound scenes - many islands, millions of points). EDYNHIP_DF_LANES forces one.
-        static const uint32_t env_lanes = getenv("EDYNHIP_DF_LANES") ? (uint32_t)atoi(getenv("EDYNHIP_DF_LANES")) : 0u;
-        static const bool two_lane_env = !(getenv("EDYNHIP_DF_TWOLANE") && getenv("EDYNHIP_DF_TWOLANE")[0] == '0');
-        static const uint32_t env_waves = getenv("EDYNHIP_DF_WAVES") ? (uint32_t)atoi(getenv("EDYNHIP_DF_WAVES")) : 0u;
         // (the multi-lane forms read J_lin on two lanes: ~20 % more row traffic, which only matters once the sweep is
         // bandwidth-bound - then the one-lane kernel is the better one)
         const bool latency_bound = c->df2_waves > 0 && na <= 16u * 32u * c->df2_waves;
@@ -3847,127 +2816,246 @@ int solve(edynhip_ctx *c) {
         // wave and sweep, and the two contend for the issue slots exactly while the critical chain runs: 0.60 vs 0.564 ms per solve.
         // Two lanes stay the default; EDYNHIP_DF_LANES=4 selects the four-lane kernel (bit-identical).
         uint32_t lanes = latency_bound ? 2u : 1u;
-        if (env_lanes == 1u || env_lanes == 2u || env_lanes == 4u) lanes = env_lanes;
-        if (!two_lane_env && lanes > 1u) lanes = 1u;
+        if (kn.df_lanes == 1 || kn.df_lanes == 2 || kn.df_lanes == 4) lanes = (uint32_t)kn.df_lanes;
         if (lanes == 4u && c->df4_waves == 0) lanes = 2u;
         if (lanes == 2u && c->df2_waves == 0) lanes = 1u;
-        const bool two_lane = lanes == 2u, four_lane = lanes == 4u;
-        df_two_lane = two_lane; df_four_lane = four_lane;
         const uint32_t per_wave = 64u / lanes;
-        const uint32_t resident = four_lane ? c->df4_waves : two_lane ? c->df2_waves : c->df_lanes;
-        const uint32_t want_waves = env_waves ? env_waves : std::max(four_lane ? 2048u : two_lane ? 1024u : 512u, blocks(na, per_wave * 9));
-        const uint32_t grid = std::min(blocks(na, per_wave), std::min(resident, want_waves));
-        static const uint32_t env_nap = getenv("EDYNHIP_DF_NAP") ? (uint32_t)atoi(getenv("EDYNHIP_DF_NAP")) : 1u;   // (r04 sweep on one box: 4 -> 1: +0.6 %, 0: the same)
+        const uint32_t resident = lanes == 4u ? c->df4_waves : lanes == 2u ? c->df2_waves : c->df_lanes;
+        const uint32_t want_waves = kn.df_waves ? (uint32_t)kn.df_waves : std::max(lanes == 4u ? 2048u : lanes == 2u ? 1024u : 512u, blocks(na, per_wave * 9));
+        p.lanes = lanes;
+        p.vel_grid = std::min(blocks(na, per_wave), std::min(resident, want_waves));
+    }
+    // one error array per position iteration (DfPosArgs::err_out / err_prev): kMaxDfPosIters of them are allocated
+    // (the dataflow position kernel hands positions and orientations over, not origins: worlds with centre-of-mass offsets solve positions per colour)
+    const uint32_t P = c->cfg.num_position_iterations;
+    p.pos_df = P > 0 && P <= kMaxDfPosIters && p.push && c->df_mode == 1 && kn.dataflow_pos && !c->b.com;
+    // resident waves: 512 for the block form (round 4: 256 / 768 / 1024 / 2048 within 1 %), 1024 - every SIMD - for the point-by-point form, whose tasks
+    // are longer (round 5, one box: 785-791 -> 796-797 steps/s; 384: 743)
+    if (p.pos_df) p.pos_grid = std::min(blocks(na, 32), std::min(c->dfp_waves, kn.dfp_waves ? (uint32_t)kn.dfp_waves : std::max(p.block_pos ? 512u : 1024u, blocks(na, 32 * 9))));
+    return p;
+}
+
+// Row preparation of the first `count` lanes of the sorted order (by_key: over ALL manifolds, the active ones tell themselves by their keys).
+// (The compiler emits template kernels in the order the host code first names them, and the code it generates for OTHER kernels of this
+//  file moves with that order - k_contact_solve<true, true, true> did when k_prep_contacts<true> was first named after the position
+//  kernels. scripts/isa_identity.py compares a tree's kernels with another's.)
+static void prep_contacts(edynhip_ctx *c, uint32_t count, bool push, bool by_key, bool pw) {
+    const Manifolds &mf = c->m[c->cur];
+    if (!c->extras) hipLaunchKernelGGL(k_prep_contacts<false>, dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
+    else hipLaunchKernelGGL(k_prep_contacts<true>, dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
+}
+
+// Islands with joints (or contact_extras rows): bucket this step's constraints by island for the island-fused kernels, and confirm the
+// plan - made from the PREVIOUS step's island sizes - with this step's.
+static int bucket_islands(edynhip_ctx *c, SolvePlan &p) {
+    hipStream_t s = c->stream;
+    const Joints &j = c->j;
+    const uint32_t n = c->b.n, na = p.na;
+    const IslLists isl{c->isl_cnt, c->isl_off, c->isl_list, c->isl_items, c->isl_sorted, c->isl_joint};
+    JointColours jc{};
+    jc.n = j.num_colours;
+    for (uint32_t k = 0; k <= j.num_colours && k <= kMaxColours; ++k) jc.start[k] = j.colour_start[k];
+    // A world of joints only (no contact this step, no sleeping) whose bodies and joints have not been edited since the lists were
+    // built has the same islands and the same lists: they are kept (chains16k: 4 launches of 28 per step)
+    const bool keep_lists = na == 0 && !c->sleep_active() && c->isl_lists_epoch == c->topology_epoch;
+    if (!keep_lists) {
+        EH_HIP(c, hipMemsetAsync(&c->cnt->isl_num, 0, 4 * sizeof(uint32_t), s));   // isl_num, isl_max_items, isl_max_jitems, isl_free
+        hipLaunchKernelGGL(k_isl_count, dim3(blocks(j.n + na, 256)), dim3(256), 0, s, j.n, na, j, c->rows, c->b, isl);
+        EH_TRY(scan_u32(c, c->isl_cnt, c->isl_off, n + 1));
+        hipLaunchKernelGGL(k_isl_fill, dim3(blocks(j.n + na, 256)), dim3(256), 0, s, j.n, na, j, jc, c->rows, c->col_keys_sorted, c->b, isl, c->cnt);
+        c->isl_lists_epoch = (na == 0 && !c->sleep_active()) ? c->topology_epoch : 0xFFFFFFFFu;
+    }
+    if (p.largest == 0xFFFFFFFFu && c->last_fetch_step != c->step_index) {
+        // no contacts and nothing with a shape: the step reads no counters at all and the islands are those of the
+        // joints, fixed until the scene is edited - read this step's values once and keep them
+        EH_TRY(fetch_counters(c, sizeof(Counters) - sizeof(uint32_t) * 8 * kMaxColours));
+        p.set_largest(c->isl_cache_max = c->cnt_host->isl_max_items);
+        c->isl_cache_jmax = c->cnt_host->isl_max_jitems; c->isl_cache_free = c->cnt_host->isl_free;
+        c->isl_cache_epoch = c->topology_epoch;
+    }
+    c->isl_prep_step = c->step_index;
+    // The decision above came from the PREVIOUS step's islands. Islands can merge in one step (a rag doll falls onto the pile), and
+    // a wave that finds itself with a 100 000-constraint island would need a large fraction of a second for it: confirm with this
+    // step's sizes (one more counter fetch, ~15 us, only on the fused / mixed schedules and only when the lists were rebuilt)
+    if ((p.isl_fused || p.mixed) && !keep_lists) {
+        EH_TRY(fetch_counters(c, sizeof(Counters) - sizeof(uint32_t) * 8 * kMaxColours));
+        if (p.isl_fused && c->cnt_host->isl_max_items > kIslFusedLimit) p.isl_fused = false;
+        if (p.mixed && c->cnt_host->isl_max_jitems > kIslFusedLimit) {   // the jointed islands outgrew the fused kernels: the whole step per colour
+            p.mixed = false; p.push = false; p.drop_dataflow();
+            if (na) prep_contacts(c, na, false, false, false);
+        }
+    }
+    return EDYNHIP_OK;
+}
+static IslSolveArgs island_args(edynhip_ctx *c, const SolvePlan &p, uint32_t iters) {
+    const IslLists isl{c->isl_cnt, c->isl_off, c->isl_list, c->isl_items, c->isl_sorted, c->isl_joint};
+    return IslSolveArgs{isl, c->cnt, c->j, c->b, c->rows, c->m[c->cur], c->m[c->cur].cap, c->extras ? c->rows.rwx : nullptr, iters, c->isl_err, c->isl_done, p.mixed ? 1u : 0u};
+}
+
+// Developer aid: EDYNHIP_DF_TRACE=<file> / EDYNHIP_DFP_TRACE=<file> with EDYNHIP_DF_TRACE_STEP=<n> dump four timestamps per task of the
+// context's n-th dataflow velocity / position solve. File: {tasks, stride, sweeps, tasks per wave}, the tasks' sorted colour keys, the
+// timestamps ("sweeps" = position iterations in a position trace: scripts/df_trace.py reads both).
+struct DfTrace {
+    uint64_t *dev = nullptr;
+    size_t words = 0;
+    static bool wanted(const std::string &path, long step, long *solves) { return !path.empty() && (*solves)++ == step; }
+    int begin(edynhip_ctx *c, size_t n) {
+        words = n;
+        EH_HIP(c, hipMalloc((void **)&dev, words * 8));
+        EH_HIP(c, hipMemsetAsync(dev, 0, words * 8, c->stream));
+        return EDYNHIP_OK;
+    }
+    int end(edynhip_ctx *c, const std::string &path, bool write, uint32_t na, uint32_t stride, uint32_t sweeps, uint32_t per_wave) {
+        if (!dev) return EDYNHIP_OK;
+        if (write) {
+            std::vector<uint64_t> tr(words); std::vector<uint32_t> keys(na);
+            EH_HIP(c, hipStreamSynchronize(c->stream));
+            EH_HIP(c, hipMemcpy(tr.data(), dev, words * 8, hipMemcpyDeviceToHost));
+            EH_HIP(c, hipMemcpy(keys.data(), c->col_keys_sorted, (size_t)na * 4, hipMemcpyDeviceToHost));
+            if (FILE *f = fopen(path.c_str(), "wb")) {
+                const uint32_t hdr[4] = {na, stride, sweeps, per_wave};
+                fwrite(hdr, 4, 4, f); fwrite(keys.data(), 4, na, f); fwrite(tr.data(), 8, words, f); fclose(f);
+            }
+        }
+        (void)hipFree(dev);
+        dev = nullptr;
+        return EDYNHIP_OK;
+    }
+};
+
+// The per-colour schedule's velocity launches: one per joint colour, one per contact colour (the small trailing colours share one).
+static void joints_pass(edynhip_ctx *c, bool warm, uint32_t *launches) {
+    hipStream_t s = c->stream;
+    const Joints &j = c->j;
+    for (uint32_t k = 0; k < j.num_colours; ++k) {
+        uint32_t a = j.colour_start[k], e = j.colour_start[k + 1];
+        if (e <= a) continue;
+        if (warm) hipLaunchKernelGGL(k_joint_solve<true>, dim3(blocks(e - a, 128)), dim3(128), 0, s, a, e, j, c->b);
+        else hipLaunchKernelGGL(k_joint_solve<false>, dim3(blocks(e - a, 128)), dim3(128), 0, s, a, e, j, c->b);
+        ++*launches;
+    }
+}
+static void contacts_pass(edynhip_ctx *c, const SolvePlan &p, bool warm, uint32_t *launches) {
+    hipStream_t s = c->stream;
+    const Rows &r = c->rows;
+    const uint32_t rcap = c->m[c->cur].cap;
+    const bool push = p.push, fused_rows = p.fused_rows;
+    for (uint32_t k = 0; k < p.first_tail; ++k) {
+        uint32_t a = c->colour_start[k], e = c->colour_end[k];
+        if (e <= a) continue;
+        const Split sp{c->colour_split[k][0], c->colour_split[k][1], c->colour_split[k][2]};
+        const dim3 g(blocks(e - a, 64)), bl(64);
+        if (push) hipLaunchKernelGGL(contact_solve_fn(warm, true, fused_rows), g, bl, 0, s, a, e, sp, (const uint32_t *)r.next, (const uint32_t *)nullptr, r.rw, rcap, r.dslot, (const float *)r.im, (float4 *)nullptr);
+        else hipLaunchKernelGGL(contact_solve_fn(warm, false, fused_rows), g, bl, 0, s, a, e, sp, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, (const float *)nullptr, c->extras ? r.rwx : (float4 *)nullptr);
+        ++*launches;
+    }
+    if (p.tail.n) {
+        const dim3 g(1), bl(kTailThreads);
+        if (push) hipLaunchKernelGGL(contact_tail_fn(warm, true, fused_rows), g, bl, 0, s, p.tail, (const uint32_t *)r.next, (const uint32_t *)nullptr, r.rw, rcap, r.dslot, (const float *)r.im, (float4 *)nullptr);
+        else hipLaunchKernelGGL(contact_tail_fn(warm, false, fused_rows), g, bl, 0, s, p.tail, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, (const float *)nullptr, c->extras ? r.rwx : (float4 *)nullptr);
+        ++*launches;
+    }
+    if (p.serial) {
+        const uint32_t a = c->colour_start[kSerialColour], e = c->colour_end[kSerialColour];
+        const Split sp{c->colour_split[kSerialColour][0], c->colour_split[kSerialColour][1], c->colour_split[kSerialColour][2]};
+        hipLaunchKernelGGL(contact_serial_fn(warm, fused_rows), dim3(1), dim3(64), 0, s, a, e, sp, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, c->extras ? r.rwx : (float4 *)nullptr);
+        ++*launches;
+    }
+}
+// The velocity solve: the dataflow launch, the island-fused kernel (beside it on the mixed schedule), or the per-colour passes. A
+// resident launch that the runtime refuses takes the dataflow launches out of the plan, and out of the context's later steps.
+static int launch_velocity(edynhip_ctx *c, SolvePlan &p, uint32_t *launches) {
+    hipStream_t s = c->stream;
+    const Knobs &kn = c->knobs;
+    if (p.lanes) {
+        const Rows &r = c->rows;
+        const uint32_t na = p.na, grid = p.vel_grid, per_wave = 64u / p.lanes;
         // (measured, round 5, A/B on one box: the headline pile LOSES - velocity solve 0.553 -> 0.597 ms: the class padding adds 6 % task slots to waves
         //  that were exactly as busy as the chains are long - mixed32k and pile8k win 1.5-3 % of their solves: off by default, EDYNHIP_DF_XCD=1 turns it on)
-        static const bool xcd_env = getenv("EDYNHIP_DF_XCD") && getenv("EDYNHIP_DF_XCD")[0] == '1';
-        const uint32_t xcd_lists = (xcd_env && two_lane && grid % kXcds == 0 && grid >= 8 * kXcds) ? 1u : 0u;
-        DfArgs a{na, grid * per_wave, c->cfg.num_velocity_iterations + 1, c->col_keys_sorted, r.next, r.im, r.rw, rcap, r.dslot, c->cnt, nullptr, df_skip, env_nap, xcd_lists};
-        // developer aid: EDYNHIP_DF_TRACE=<file> EDYNHIP_DF_TRACE_STEP=<n> dumps per-task timestamps of the n-th solve
-        static const char *trace_path = getenv("EDYNHIP_DF_TRACE");
-        static long trace_step = getenv("EDYNHIP_DF_TRACE_STEP") ? atol(getenv("EDYNHIP_DF_TRACE_STEP")) : 100, solve_calls = 0;
-        const bool tracing = trace_path && solve_calls++ == trace_step;
-        size_t trace_words = 0;
-        if (tracing) a.xcd_lists = 0;   // (the trace is laid out by (sweep, round, wave) of the plain assignment)
-        if (tracing) {
+        const uint32_t xcd_lists = (kn.df_xcd && p.lanes == 2u && grid % kXcds == 0 && grid >= 8 * kXcds) ? 1u : 0u;
+        DfArgs a{na, grid * per_wave, c->cfg.num_velocity_iterations + 1, c->col_keys_sorted, r.next, r.im, r.rw, c->m[c->cur].cap, r.dslot, c->cnt, nullptr, p.df_skip(c),
+                 (uint32_t)kn.df_nap, xcd_lists};   // (EDYNHIP_DF_NAP, r04 sweep on one box: 4 -> 1: +0.6 %, 0: the same)
+        DfTrace trace;
+        if (DfTrace::wanted(kn.df_trace, kn.df_trace_step, &c->df_solves)) {
+            a.xcd_lists = 0;   // (the trace is laid out by (sweep, round, wave) of the plain assignment)
             const uint32_t rounds = (na + a.stride - 1) / a.stride;
-            trace_words = 4 * (size_t)a.sweeps * rounds * (a.stride / per_wave);
-            EH_HIP(c, hipMalloc((void **)&a.trace, trace_words * 8));
-            EH_HIP(c, hipMemsetAsync(a.trace, 0, trace_words * 8, s));
+            EH_TRY(trace.begin(c, 4 * (size_t)a.sweeps * rounds * (a.stride / per_wave)));
+            a.trace = trace.dev;
         }
         void *params[] = {&a};
         // cooperative launch: the runtime guarantees that all `grid` workgroups are resident together, which the
         // hand-off polling relies on
-        if (launch_resident(c, df_velocity_fn(lanes, fused_rows), grid, 64, params) == hipSuccess) {
-            df_velocity = true;
-            ++launches;
+        if (launch_resident(c, df_velocity_fn(p.lanes, p.fused_rows), grid, 64, params) == hipSuccess) {
+            ++*launches;
         } else {   // e.g. the device is shared and cannot hold the grid: use the per-colour schedule from now on
             (void)hipGetLastError();
             c->df_mode = 0;
+            p.drop_dataflow();
             // the mixed schedule has no per-colour form for THIS step (the chains skip the jointed islands): give the step up,
             // the next one takes the per-colour launches
-            if (mixed) return set_error(c, EDYNHIP_ERR_INTERNAL, "solve: the runtime refused the resident launch of the mixed schedule");
-        }
-        if (tracing && df_velocity) {
-            std::vector<uint64_t> tr(trace_words); std::vector<uint32_t> keys(na);
-            EH_HIP(c, hipStreamSynchronize(s));
-            EH_HIP(c, hipMemcpy(tr.data(), a.trace, trace_words * 8, hipMemcpyDeviceToHost));
-            EH_HIP(c, hipMemcpy(keys.data(), c->col_keys_sorted, (size_t)na * 4, hipMemcpyDeviceToHost));
-            if (FILE *f = fopen(trace_path, "wb")) {
-                const uint32_t hdr[4] = {na, a.stride, a.sweeps, per_wave};
-                fwrite(hdr, 4, 4, f); fwrite(keys.data(), 4, na, f); fwrite(tr.data(), 8, trace_words, f); fclose(f);
+            if (p.mixed) {
+                (void)trace.end(c, kn.df_trace, false, na, a.stride, a.sweeps, per_wave);
+                return set_error(c, EDYNHIP_ERR_INTERNAL, "solve: the runtime refused the resident launch of the mixed schedule");
             }
-            (void)hipFree(a.trace);
-        } else if (tracing) (void)hipFree(a.trace);
+        }
+        EH_TRY(trace.end(c, kn.df_trace, p.lanes != 0, na, a.stride, a.sweeps, per_wave));
     }
-    if ((!df_velocity && isl_fused) || (df_velocity && mixed)) {   // mixed: the islands with joints, beside the dataflow launch
-        isl_args.iters = c->cfg.num_velocity_iterations;
-        if (fused_rows) hipLaunchKernelGGL(k_island_velocity<true>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
+    if ((!p.lanes && p.isl_fused) || (p.lanes && p.mixed)) {   // mixed: the islands with joints, beside the dataflow launch
+        const IslSolveArgs isl_args = island_args(c, p, c->cfg.num_velocity_iterations);
+        if (p.fused_rows) hipLaunchKernelGGL(k_island_velocity<true>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
         else hipLaunchKernelGGL(k_island_velocity<false>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
-        ++launches;
-    } else if (!df_velocity) {
-        joints_pass(true);
-        contacts_pass(true);
+        ++*launches;
+    } else if (!p.lanes) {
+        joints_pass(c, true, launches);
+        contacts_pass(c, p, true, launches);
         for (uint32_t it = 0; it < c->cfg.num_velocity_iterations; ++it) {
-            joints_pass(false);
-            contacts_pass(false);
+            joints_pass(c, false, launches);
+            contacts_pass(c, p, false, launches);
         }
     }
-    c->timings.solve_velocity_launches += launches;
-    c->stats.solve_schedule = (na + j.n) == 0 ? EDYNHIP_SCHEDULE_NONE
-                              : df_velocity ? (mixed ? EDYNHIP_SCHEDULE_MIXED : df_four_lane ? EDYNHIP_SCHEDULE_DATAFLOW4 : df_two_lane ? EDYNHIP_SCHEDULE_DATAFLOW2 : EDYNHIP_SCHEDULE_DATAFLOW1)
-                              : isl_fused ? EDYNHIP_SCHEDULE_ISLAND_FUSED : EDYNHIP_SCHEDULE_PER_COLOUR;
-    rec(c, 6);
-    static const bool pos_df_env = !(getenv("EDYNHIP_DATAFLOW_POS") && getenv("EDYNHIP_DATAFLOW_POS")[0] == '0');
-    const uint32_t P = c->cfg.num_position_iterations;
-    // one error array per position iteration (DfPosArgs::err_out / err_prev): kMaxDfPosIters of them are allocated
-    // (the dataflow position kernel hands positions and orientations over, not origins: worlds with centre-of-mass offsets solve positions per colour)
-    const bool pos_df = P > 0 && P <= kMaxDfPosIters && push && c->df_mode == 1 && pos_df_env && !c->b.com;
-    hipLaunchKernelGGL(k_integrate, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, dt, c->isl_err, c->isl_done, push ? c->rows.dslot : nullptr, c->rows.first_slot,
-                       c->pos_err, pos_df ? P : 0u);
-    if (na && !pos_df) hipLaunchKernelGGL(k_store_impulses, dim3(blocks(na, 256)), dim3(256), 0, s, na, c->rows, rcap, mf);
-    rec(c, 7);
-    const float4 *final_pslot = nullptr;   // set while the bodies' final transforms still live in the hand-off slots
-    auto pos_per_colour = [&](uint32_t first_it) {
-        for (uint32_t it = first_it; it < c->cfg.num_position_iterations; ++it) {
-            for (uint32_t k = 0; k < j.num_colours; ++k) {
-                uint32_t a = j.colour_start[k], e = j.colour_start[k + 1];
-                if (e > a) hipLaunchKernelGGL(k_pos_joints, dim3(blocks(e - a, 128)), dim3(128), 0, s, a, e, j, c->b, c->isl_err, c->isl_done);
-            }
-            for (uint32_t k = 0; k < first_tail; ++k) {
-                uint32_t a = c->colour_start[k], e = c->colour_end[k];
-                if (e > a) hipLaunchKernelGGL(block_pos ? k_pos_contacts<true> : k_pos_contacts<false>, dim3(blocks(2 * (e - a), 128)), dim3(128), 0, s, a, e, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
-            }
-            if (tail.n) hipLaunchKernelGGL(block_pos ? k_pos_contacts_tail<true> : k_pos_contacts_tail<false>, dim3(1), dim3(256), 0, s, tail, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
-            if (serial) hipLaunchKernelGGL(block_pos ? k_pos_contacts_serial<true> : k_pos_contacts_serial<false>, dim3(1), dim3(64), 0, s, c->colour_start[kSerialColour], c->colour_end[kSerialColour], c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
-            hipLaunchKernelGGL(k_pos_flags, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->isl_err, c->isl_done);
+    return EDYNHIP_OK;
+}
+
+static void pos_per_colour(edynhip_ctx *c, const SolvePlan &p, uint32_t first_it) {
+    hipStream_t s = c->stream;
+    const Joints &j = c->j;
+    const Manifolds &mf = c->m[c->cur];
+    const uint32_t n = c->b.n;
+    const bool block_pos = p.block_pos;
+    for (uint32_t it = first_it; it < c->cfg.num_position_iterations; ++it) {
+        for (uint32_t k = 0; k < j.num_colours; ++k) {
+            uint32_t a = j.colour_start[k], e = j.colour_start[k + 1];
+            if (e > a) hipLaunchKernelGGL(k_pos_joints, dim3(blocks(e - a, 128)), dim3(128), 0, s, a, e, j, c->b, c->isl_err, c->isl_done);
         }
-    };
-    if (pos_df) {
-        static const uint32_t env_pw = getenv("EDYNHIP_DFP_WAVES") ? (uint32_t)atoi(getenv("EDYNHIP_DFP_WAVES")) : 0u;
+        for (uint32_t k = 0; k < p.first_tail; ++k) {
+            uint32_t a = c->colour_start[k], e = c->colour_end[k];
+            if (e > a) hipLaunchKernelGGL(block_pos ? k_pos_contacts<true> : k_pos_contacts<false>, dim3(blocks(2 * (e - a), 128)), dim3(128), 0, s, a, e, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
+        }
+        if (p.tail.n) hipLaunchKernelGGL(block_pos ? k_pos_contacts_tail<true> : k_pos_contacts_tail<false>, dim3(1), dim3(256), 0, s, p.tail, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
+        if (p.serial) hipLaunchKernelGGL(block_pos ? k_pos_contacts_serial<true> : k_pos_contacts_serial<false>, dim3(1), dim3(64), 0, s, c->colour_start[kSerialColour], c->colour_end[kSerialColour], c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
+        hipLaunchKernelGGL(k_pos_flags, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->isl_err, c->isl_done);
+    }
+}
+// The position solve. *final_pslot is set while the bodies' final transforms still live in the hand-off slots (k_finish picks them up).
+static int launch_position(edynhip_ctx *c, const SolvePlan &p, const float4 **final_pslot) {
+    hipStream_t s = c->stream;
+    const Knobs &kn = c->knobs;
+    const Manifolds &mf = c->m[c->cur];
+    const uint32_t n = c->b.n, na = p.na, P = c->cfg.num_position_iterations;
+    const bool block_pos = p.block_pos;
+    if (p.pos_df) {
         const Rows &r = c->rows;
-        hipLaunchKernelGGL(k_pos_seed, dim3(blocks(2 * na, 256)), dim3(256), 0, s, na, r, c->b, r.pslot, rcap, mf, df_skip);
-        // resident waves: 512 for the block form (round 4: 256 / 768 / 1024 / 2048 within 1 %), 1024 - every SIMD - for the point-by-point form, whose tasks
-        // are longer (round 5, one box: 785-791 -> 796-797 steps/s; 384: 743)
-        const uint32_t grid = std::min(blocks(na, 32), std::min(c->dfp_waves, env_pw ? env_pw : std::max(block_pos ? 512u : 1024u, blocks(na, 32 * 9))));
-        // developer aid: EDYNHIP_DFP_TRACE=<file> EDYNHIP_DF_TRACE_STEP=<n> dumps per-task timestamps of the n-th position solve
-        // (same file format as EDYNHIP_DF_TRACE with "sweeps" = position iterations: scripts/df_trace.py reads both)
-        static const char *ptrace_path = getenv("EDYNHIP_DFP_TRACE");
-        static long ptrace_step = getenv("EDYNHIP_DF_TRACE_STEP") ? atol(getenv("EDYNHIP_DF_TRACE_STEP")) : 100, pos_calls = 0;
-        const bool ptracing = ptrace_path && pos_calls++ == ptrace_step;
+        const uint32_t grid = p.pos_grid;
+        hipLaunchKernelGGL(k_pos_seed, dim3(blocks(2 * na, 256)), dim3(256), 0, s, na, r, c->b, r.pslot, mf.cap, mf, p.df_skip(c));
         const uint32_t prounds = blocks(na, grid * 32u);
         const size_t ptrace_words = 4 * (size_t)prounds * grid;
-        uint64_t *ptrace = nullptr;
-        if (ptracing) {
-            EH_HIP(c, hipMalloc((void **)&ptrace, ptrace_words * P * 8));
-            EH_HIP(c, hipMemsetAsync(ptrace, 0, ptrace_words * P * 8, s));
-        }
+        DfTrace trace;
+        if (DfTrace::wanted(kn.dfp_trace, kn.df_trace_step, &c->dfp_solves)) EH_TRY(trace.begin(c, ptrace_words * P));
         uint32_t it = 0;
-        for (; it < c->cfg.num_position_iterations; ++it) {
-            static const bool xcd_env = getenv("EDYNHIP_DF_XCD") && getenv("EDYNHIP_DF_XCD")[0] == '1';
-            const uint32_t xcd_lists = (xcd_env && !ptrace && grid % kXcds == 0 && grid >= 8 * kXcds) ? 1u : 0u;
+        for (; it < P; ++it) {
+            const uint32_t xcd_lists = (kn.df_xcd && !trace.dev && grid % kXcds == 0 && grid >= 8 * kXcds) ? 1u : 0u;
             DfPosArgs a{na, grid * 32u, it, c->col_keys_sorted, r.next, r.pslot, r, mf, c->b, c->pos_err + (size_t)it * c->b.cap,
-                        it ? c->pos_err + (size_t)(it - 1) * c->b.cap : nullptr, c->cnt, df_skip, ptrace ? ptrace + ptrace_words * it : nullptr, xcd_lists};
+                        it ? c->pos_err + (size_t)(it - 1) * c->b.cap : nullptr, c->cnt, p.df_skip(c), trace.dev ? trace.dev + ptrace_words * it : nullptr, xcd_lists};
             void *params[] = {&a};
             if (launch_resident(c, df_position_fn(block_pos), grid, 64, params) != hipSuccess) {
                 (void)hipGetLastError();
@@ -3975,38 +3063,93 @@ int solve(edynhip_ctx *c) {
                 break;
             }
         }
-        if (ptrace) {
-            std::vector<uint64_t> tr(ptrace_words * P); std::vector<uint32_t> keys(na);
-            EH_HIP(c, hipStreamSynchronize(s));
-            EH_HIP(c, hipMemcpy(tr.data(), ptrace, tr.size() * 8, hipMemcpyDeviceToHost));
-            EH_HIP(c, hipMemcpy(keys.data(), c->col_keys_sorted, (size_t)na * 4, hipMemcpyDeviceToHost));
-            if (FILE *f = fopen(ptrace_path, "wb")) {
-                const uint32_t hdr[4] = {na, grid * 32u, P, 32u};
-                fwrite(hdr, 4, 4, f); fwrite(keys.data(), 4, na, f); fwrite(tr.data(), 8, tr.size(), f); fclose(f);
-            }
-            (void)hipFree(ptrace);
-        }
+        EH_TRY(trace.end(c, kn.dfp_trace, true, na, grid * 32u, P, 32u));
         // the bodies' transforms live in the hand-off slots while the dataflow launches run; k_finish picks them up
         if (it == P) {
-            final_pslot = r.pslot;
-            if (mixed) {   // the islands with joints, on the body records
-                isl_args.iters = P;
+            *final_pslot = r.pslot;
+            if (p.mixed) {   // the islands with joints, on the body records
+                const IslSolveArgs isl_args = island_args(c, p, P);
                 hipLaunchKernelGGL(block_pos ? k_island_position<true> : k_island_position<false>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
             }
-        } else if (mixed) {
+        } else if (p.mixed) {
             return set_error(c, EDYNHIP_ERR_INTERNAL, "solve: the runtime refused the resident launch of the mixed schedule (position)");
         } else {   // a cooperative launch was refused: finish per colour (rare; never on an exclusive device)
             hipLaunchKernelGGL(k_pos_writeback, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, r.pslot, r.first_slot);
             if (it > 0) hipLaunchKernelGGL(k_pos_flags, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->pos_err + (size_t)(it - 1) * c->b.cap, c->isl_done);
-            pos_per_colour(it);
+            pos_per_colour(c, p, it);
         }
-    } else if (P > 0 && (na || j.n)) {
-        if (isl_fused) {
-            isl_args.iters = P;
+    } else if (P > 0 && (na || c->j.n)) {
+        if (p.isl_fused) {
+            const IslSolveArgs isl_args = island_args(c, p, P);
             hipLaunchKernelGGL(block_pos ? k_island_position<true> : k_island_position<false>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
-        } else pos_per_colour(0);
+        } else pos_per_colour(c, p, 0);
     }
+    return EDYNHIP_OK;
+}
+
+// One step's solve: probe (once per context), colour, plan, prepare the rows, velocity solve, integrate, position solve, finish.
+int solve(edynhip_ctx *c) {
+    hipStream_t s = c->stream;
+    const uint32_t n = c->b.n;
+    if (n == 0) return EDYNHIP_OK;
+    Manifolds &mf = c->m[c->cur];
+    const Joints &j = c->j;
+    const float dt = c->cfg.fixed_dt;
+    const uint32_t rcap = mf.cap;
+    rec(c, 3);
+    EH_TRY(restitution(c));   // solve_restitution comes first in solver::update (solver.cpp:397); a no-op without bouncy materials
+    // gravity / zeroed deltas do not depend on the colouring: enqueued first, they run while the host waits for the counters
+    if (!c->solve_begin_done) hipLaunchKernelGGL(k_solve_begin, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, dt, c->rows.first_slot);
+    c->solve_begin_done = false;
+    // Contact-only scenes: the whole velocity solve as one dataflow launch (see k_contact_solve_df).
+    if (c->df_mode < 0) probe_dataflow(c, (c->cfg.flags & EDYNHIP_FLAG_FUSED_VELOCITY_ROWS) != 0, (c->cfg.flags & EDYNHIP_FLAG_BLOCK_POSITION) != 0);
+    // Contact-only worlds on the dataflow schedule: the row preparation does not wait for the host to read the colouring's counters.
+    // It is enqueued right behind the counter publish over ALL manifolds - the active ones are the prefix of the sorted order whose
+    // keys name a colour (k_prep_contacts by_key) - and runs while the answer travels to the host and the next launches travel back
+    // (14 us of idle GPU per step on the headline pile, profiles/r04_timeline_pile32k.txt). If the colouring turns out unfinished
+    // (uncoloured edges left for the multi-block rounds: a scene coloured from scratch) the rows are prepared again after the second sort;
+    // a non-empty serial bucket only drops `push` - the slot table written for it is read through the bodies' colour masks alone.
+    bool spec_prep = false;
+    auto speculative_prep = [&]() {
+        rec(c, 4);
+        if (!(c->knobs.speculate && j.n == 0 && !c->extras && c->df_mode == 1 && c->full_step && c->num_manifolds > 0)) return;
+        prep_contacts(c, c->num_manifolds, true, true, kPwInPrep);
+        spec_prep = true;
+    };
+    bool first_final = false;
+    EH_TRY(colour_contacts(c, speculative_prep, &first_final));
+    if (!first_final) spec_prep = false;   // the sorted order changed after the speculative launch: prepare again
+    // colour_contacts fetched the counters: with island sleeping, remember whether anything is still awake
+    c->all_asleep = c->sleep_active() && c->full_step && c->num_manifolds > 0 && c->cnt_host->num_awake == 0;
+    if (c->num_manifolds == 0) rec(c, 4);
+    if (j.n) hipLaunchKernelGGL(k_prep_joints, dim3(blocks(j.n, 128)), dim3(128), 0, s, j, c->b, dt, c->isl_joint);
+    if (j.n && c->has_generic) hipLaunchKernelGGL(k_prep_generic, dim3(blocks(j.n, 64)), dim3(64), 0, s, j, c->b, dt);
+
+    SolvePlan p = plan_solve(c);
+    const uint32_t na = p.na;
+
+    if (na && !spec_prep) prep_contacts(c, na, p.push, false, !c->extras && kPwInPrep);
+    if (p.isl_candidate) EH_TRY(bucket_islands(c, p));
+    if (p.push) {
+        hipLaunchKernelGGL(k_push_links, dim3(blocks(na, 256)), dim3(256), 0, s, na, c->rows, c->col_keys_sorted, c->b, c->used, p.mixed ? c->isl_joint : nullptr);
+    }
+    rec(c, 5);
+
+    uint32_t launches = 0;
+    EH_TRY(launch_velocity(c, p, &launches));
+    c->timings.solve_velocity_launches += launches;
+    c->stats.solve_schedule = p.schedule(j.n);
+    rec(c, 6);
+
+    hipLaunchKernelGGL(k_integrate, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, dt, c->isl_err, c->isl_done, p.push ? c->rows.dslot : nullptr, c->rows.first_slot,
+                       c->pos_err, p.pos_df ? c->cfg.num_position_iterations : 0u);
+    if (na && !p.pos_df) hipLaunchKernelGGL(k_store_impulses, dim3(blocks(na, 256)), dim3(256), 0, s, na, c->rows, rcap, mf);
+    rec(c, 7);
+
+    const float4 *final_pslot = nullptr;
+    EH_TRY(launch_position(c, p, &final_pslot));
     rec(c, 8);
+
     hipLaunchKernelGGL(k_finish, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, c->used, c->m[c->cur ^ 1].seg_start, c->m[c->cur ^ 1].seg_end, c->cnt,
                        final_pslot, c->rows.first_slot, CandLists{c->bvh.cand_list, c->bvh.cand_count, c->bvh.ref_min, c->bvh.ref_max}, c->isl_joint, c->isl_top, c->meshes);
     rec(c, 9);

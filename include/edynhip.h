@@ -342,7 +342,7 @@ int edynhip_query_aabb_device(edynhip_ctx *ctx, int category, uint32_t n, const 
 /* Statistics since the context was created, counted by the fill kernels: segments one wave sorted in LDS, and queries whose hits one
  * wave packed from the body range (the second fill path of large results); every other query was filled and sorted by its own lane.
  * Calls that only count (ids = NULL, or EDYNHIP_ERR_CAPACITY) add nothing. Either pointer may be NULL.
- * Debug knob: the environment variable EDYNHIP_QUERY_SCAN_RATIO = r (read when a context answers its first query) moves the switch to
+ * Debug knob: the environment variable EDYNHIP_QUERY_SCAN_RATIO = r (read when the context is created) moves the switch to
  * the second fill path to "more than num_bodies / r hits" (default 64). It changes the cost only, never a result; it exists for
  * scripts/bench_query_aabb.py --ratios and for tests that steer queries onto one path. */
 int edynhip_query_aabb_stats(edynhip_ctx *ctx, uint64_t *wave_sorted, uint64_t *wave_filled);
