@@ -97,6 +97,15 @@ class RecordView(C.Structure):
     _fields_ = [("records", C.c_void_p), ("num_bodies", C.c_uint32), ("step_index", C.c_uint32), ("events", C.c_void_p),
                 ("num_events", C.c_uint32), ("total_events", C.c_uint32)]
 STAGE_BROADPHASE, STAGE_NARROWPHASE, STAGE_ISLANDS, STAGE_SOLVE, STAGE_ALL = 1, 2, 4, 8, 15
+# EDYNHIP_PATH_* of include/edynhip.h (edynhip_debug_paths): name -> bit of the mask
+PATH_BITS = {"COMPACT_DIRECT": 1 << 0, "COMPACT_LIBRARY": 1 << 1, "SORT_DIRECT": 1 << 2, "SORT_LIBRARY": 1 << 3, "SPECULATE": 1 << 4,
+             "INPLACE": 1 << 5, "LISTS_FORCED": 1 << 6, "LOOKAHEAD_CHANGED": 1 << 7, "RELABEL_COMPRESS0": 1 << 8,
+             "RELABEL_COMPRESS1": 1 << 9, "RELABEL_COMPRESSN": 1 << 10, "VEL_XCD": 1 << 11, "POS_XCD": 1 << 12, "VEL_LANES1": 1 << 13,
+             "VEL_LANES2": 1 << 14, "VEL_LANES4": 1 << 15, "VEL_MULTI_ROUND": 1 << 16, "POS_MULTI_ROUND": 1 << 17,
+             "POS_COLOUR_PUSH": 1 << 18, "MIXED": 1 << 19, "ISLAND_FUSED": 1 << 20, "PER_COLOUR": 1 << 21, "POLY_ONE_LANE": 1 << 22,
+             "POLY_AXES8": 1 << 23, "POLY_AXES16": 1 << 24, "POLY_CONTACTS4": 1 << 25, "POLY_CONTACTS8": 1 << 26,
+             "POLY_CONTACTS16": 1 << 27, "POLY_HINTS": 1 << 28, "RECORDS_DIRECT": 1 << 29, "RECORDS_COPY": 1 << 30,
+             "WORLD_SERIAL": 1 << 31, "VEL_NAP": 1 << 32}
 
 # every symbol include/edynhip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_set_stream", "edynhip_set_bodies",
@@ -120,7 +129,8 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_world_set_pair_filter", "edynhip_world_default_should_collide", "edynhip_get_sleep_timers", "edynhip_set_sleep_timers",
            "edynhip_raycast", "edynhip_raycast_device",
            "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats",
-           "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device"]
+           "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device",
+           "edynhip_debug_paths", "edynhip_world_debug_paths"]
 
 _lib = None
 
@@ -162,6 +172,8 @@ def lib():
         L.edynhip_get_timings.argtypes = [C.c_void_p, C.POINTER(Timings)]
         L.edynhip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.edynhip_debug_collide.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p]
+        L.edynhip_debug_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.edynhip_world_debug_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.edynhip_get_asleep.argtypes = [C.c_void_p, C.c_void_p]
         L.edynhip_wake_all.argtypes = [C.c_void_p]
         L.edynhip_wake_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]

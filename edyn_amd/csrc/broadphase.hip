@@ -731,6 +731,7 @@ int broadphase(edynhip_ctx *c) {
         // would test the wrong bodies (found by the settled C3 scene: fast spheres, lists of > 64 candidates, pairs lost in the step
         // after a topology rebuild). So a rebuild step refits and re-walks.
         const uint32_t force = (c->bvh.lists_dirty || !c->full_step || !c->knobs.bp_lists || rebuild) ? 1u : 0u;
+        if (force && !(c->bvh.lists_dirty || !c->full_step || rebuild)) c->paths |= EDYNHIP_PATH_LISTS_FORCED;
         c->bvh.lists_dirty = false;
         hipLaunchKernelGGL(k_bp_refit, dim3(blocks(np, 256)), dim3(256), 0, s, c->bvh.keys_sorted, (int)np, c->bvh.parent, c->bvh.left, c->bvh.right, c->bvh.rope, c->b.amin, c->b.amax, c->bvh.nmin, c->bvh.nmax, c->bvh.visit, c->cnt, c->bvh.ref_min, c->bvh.ref_max, c->b.linvel, c->b.angvel, c->cfg.fixed_dt, force,
                            sqrtf(c->cfg.gravity[0] * c->cfg.gravity[0] + c->cfg.gravity[1] * c->cfg.gravity[1] + c->cfg.gravity[2] * c->cfg.gravity[2]), c->bvh.lookahead);
@@ -760,8 +761,10 @@ int broadphase(edynhip_ctx *c) {
         // owners in index order: offsets = exclusive scan of the per-owner counts (own_count[n] = 0 -> own_offset[n] = total)
         const bool direct_env = c->knobs.direct_compact;   // developer knob (A/B)
         if (c->b.n <= kCompactScanBodies && direct_env) {
+            c->paths |= EDYNHIP_PATH_COMPACT_DIRECT;
             hipLaunchKernelGGL(k_bp_compact<true>, dim3(blocks(c->b.n, 256)), dim3(256), 0, s, c->b.n, c->own_keys, c->own_count, c->own_offset, c->pair_keys, c->pair_keys_sorted, cur.cap, c->cnt, prev.skey, pm);
         } else {
+            c->paths |= EDYNHIP_PATH_COMPACT_LIBRARY;
             EH_TRY(scan_u32(c, c->own_count, c->own_offset, c->b.n + 1));
             hipLaunchKernelGGL(k_bp_compact<false>, dim3(blocks(c->b.n, 256)), dim3(256), 0, s, c->b.n, c->own_keys, c->own_count, c->own_offset, c->pair_keys, c->pair_keys_sorted, cur.cap, c->cnt, prev.skey, pm);
         }
@@ -779,6 +782,7 @@ int broadphase(edynhip_ctx *c) {
         const uint32_t spec_grid = std::min<uint32_t>(cur.cap / 512u, blocks(pm + pm / 16 + 2048, 512));
         if (spec_env && c->full_step && pm > 0 && spec_grid > 0 && !c->pair_filter) {   // (a host pair filter may shorten the list first)
             covered = spec_grid * 512u;
+            c->paths |= EDYNHIP_PATH_SPECULATE;
             hipLaunchKernelGGL(k_bp_build_manifolds, dim3(spec_grid), dim3(512), 0, s, c->pair_keys_sorted, 0u, cur, prev, pm, c->cnt, c->new_edges, c->new_edge_m, false, ev, c->prev_matched,
                                0u, true, inplace_allowed);
         }
@@ -791,8 +795,10 @@ int broadphase(edynhip_ctx *c) {
             const bool rebuilt = force != 0 || c->cnt_host->bp_rebuilt != 0;
             c->bvh.rebuild_hist = (c->bvh.rebuild_hist << 1) | (rebuilt ? 1u : 0u);
             if (adapt && c->full_step) {
+                const float before = c->bvh.lookahead;
                 if ((c->bvh.rebuild_hist & 0xFu) == 0xFu) c->bvh.lookahead = std::max(kListLookaheadMin, 0.5f * c->bvh.lookahead);
                 else if (__builtin_popcount(c->bvh.rebuild_hist & 0xFFu) <= 2) c->bvh.lookahead = std::min(kListLookaheadMax, 2.0f * c->bvh.lookahead);
+                if (c->bvh.lookahead != before) c->paths |= EDYNHIP_PATH_LOOKAHEAD_CHANGED;
             }
         }
         if (c->cnt_host->num_extra) {   // some owner had more than kOwnCap partners: its surplus sits unsorted at the end
@@ -807,6 +813,7 @@ int broadphase(edynhip_ctx *c) {
         if (inplace_allowed && M > 0 && M == pm && !c->cnt_host->pairs_differ) {
             c->points_in_prev = false;
             c->inplace_step = true;
+            c->paths |= EDYNHIP_PATH_INPLACE;
             c->prev_num_manifolds = pm;
             c->num_manifolds = M;
             EH_HIP(c, hipGetLastError());

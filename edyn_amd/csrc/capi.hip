@@ -1789,6 +1789,7 @@ int edynhip_snapshot_records(edynhip_ctx *c, float present_dt, uint32_t max_even
     // (785 / 759 against 764 / 765): the shim asks for it in its synchronous write-back only. (developer knob EDYNHIP_RECORDS_DIRECT=0 / 1 overrides)
     const long direct_env = c->knobs.records_direct;
     const bool direct = direct_env >= 0 ? direct_env != 0 : (flags & EDYNHIP_SNAPSHOT_DIRECT) != 0;
+    c->paths |= direct ? EDYNHIP_PATH_RECORDS_DIRECT : EDYNHIP_PATH_RECORDS_COPY;
     if (direct) {
         if (n) hipLaunchKernelGGL(k_pack_records, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->b, present_dt, (float4 *)(h + kRecHeader + ev_bytes));
         hipLaunchKernelGGL(k_pack_events, dim3(copy_events > 4096 ? 64 : 4), dim3(256), 0, c->stream, (const eh::ContactEvent *)c->events, (const uint32_t *)c->event_count,
@@ -1904,6 +1905,12 @@ int edynhip_debug_collide(edynhip_ctx *c, uint32_t n, const int32_t *shape_type,
     if (!c || (n && (!shape_type || !shape_param || !pos || !orn || !out_points || !out_count))) return EDYNHIP_ERR_INVALID;
     EH_HIP(c, hipSetDevice(c->device));
     return debug_collide(c, n, shape_type, shape_param, pos, orn, threshold, out_points, out_count);
+}
+
+int edynhip_debug_paths(edynhip_ctx *c, uint64_t *mask) {
+    if (!c || !mask) return EDYNHIP_ERR_INVALID;
+    *mask = c->paths;
+    return EDYNHIP_OK;
 }
 
 int edynhip_get_timings(edynhip_ctx *c, edynhip_timings *out) {

@@ -499,10 +499,12 @@ int colour_contacts(edynhip_ctx *c, const std::function<void()> &between, bool *
             const uint32_t nb = blocks(M, kCsBlock);
             const bool direct_env = c->knobs.direct_sort;   // developer knob (A/B)
             if (nb <= kCsDirectBlocks && direct_env) {
+                c->paths |= EDYNHIP_PATH_SORT_DIRECT;
                 if (!first) EH_HIP(c, hipMemsetAsync(c->cs_sup, 0, (size_t)(kCsDirectBlocks / kCsSuper) * kCsKeys * sizeof(uint32_t), s));   // (the step's first sort: cleared by k_col_tops)
                 hipLaunchKernelGGL(k_cs_hist<true>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_hist, nb, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->sleeping, c->cs_sup);
                 hipLaunchKernelGGL(k_cs_scatter<true>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_hist, nb, c->col_keys_sorted, c->rows.order, c->cnt, c->cs_sup);
             } else {
+                c->paths |= EDYNHIP_PATH_SORT_LIBRARY;
                 hipLaunchKernelGGL(k_cs_hist<false>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_hist, nb, mf.info, mf.bodyA, mf.bodyB, c->b.flags, c->sleeping, (uint32_t *)nullptr);
                 EH_TRY(scan_u32(c, c->cs_hist, c->cs_start, kCsKeys * nb));
                 hipLaunchKernelGGL(k_cs_scatter<false>, dim3(nb), dim3(kCsBlock), 0, s, M, c->col_keys, c->cs_start, nb, c->col_keys_sorted, c->rows.order, c->cnt, (const uint32_t *)nullptr);

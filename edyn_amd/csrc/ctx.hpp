@@ -325,6 +325,7 @@ struct StageTimer {
 struct edynhip_ctx {
     edynhip_config cfg{};
     eh::Knobs knobs{};             // the development knobs as the environment had them when the context was created
+    uint64_t paths = 0;            // EDYNHIP_PATH_*: the host-side branches taken since creation (edynhip_debug_paths)
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = true;

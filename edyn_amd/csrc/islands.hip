@@ -328,7 +328,8 @@ int islands(edynhip_ctx *c) {
     if (mode == CC_FULL) {
         hipLaunchKernelGGL(k_cc_init, dim3(blocks(n, 256)), dim3(256), 0, s, n, forest, c->cnt, mf, M, c->b.flags);
         if (c->j.n) hipLaunchKernelGGL(k_cc_hook, dim3(blocks(c->j.n, 256)), dim3(256), 0, s, c->j.n, c->j.bodyA, c->j.bodyB, c->b.flags, forest);
-        const int compress_env = (int)c->knobs.cc_compress;   // developer knob: passes of k_cc_compress
+        const int compress_env = (int)c->knobs.cc_compress;   // developer knob: passes of k_cc_compress (the path bit: only where the step itself found the certificate broken)
+        if (M && !force) c->paths |= compress_env <= 0 ? EDYNHIP_PATH_RELABEL_COMPRESS0 : compress_env == 1 ? EDYNHIP_PATH_RELABEL_COMPRESS1 : EDYNHIP_PATH_RELABEL_COMPRESSN;
         if (M) for (int pass = 0; pass < compress_env; ++pass) hipLaunchKernelGGL(k_cc_compress, dim3(blocks(n, 256)), dim3(256), 0, s, n, forest, c->b.flags);
         // (round 5, measured and dropped: one lane per EDGE on the compressed forest instead of the per-body walks - 2 x 67 us against 57:
         //  what costs is not the depth of the finds any more but the unions themselves, thousands of trees hooking into one root)

@@ -261,6 +261,7 @@ struct Shard {
     uint32_t cap = 0, joint_cap = 0, meshes_created = 0;
     int rc = EDYNHIP_OK;
     std::string err;
+    uint64_t paths_gone = 0;              // edynhip_debug_paths of the contexts this shard had before (free_shard)
     // collected for a re-partition
     std::vector<uint32_t> labels; std::vector<float> aabb; std::vector<edynhip_manifold> manifolds; std::vector<float> imp24, imp10; std::vector<uint8_t> asleep;
     std::vector<uint32_t> sleep_label; std::vector<double> sleep_since; double sleep_clock = 0;
@@ -285,13 +286,14 @@ public:
         cv_.notify_all();
         for (auto &t : threads_) t.join();
     }
-    void run(const std::function<void(uint32_t)> &fn) {
-        if (n_ == 1) { fn(0); return; }
-        if (serial_) { for (uint32_t r = 0; r < n_; ++r) fn(r); return; }
+    bool run(const std::function<void(uint32_t)> &fn) {   // true: several shards, one after the other on the caller's thread
+        if (n_ == 1) { fn(0); return false; }
+        if (serial_) { for (uint32_t r = 0; r < n_; ++r) fn(r); return true; }
         { std::lock_guard<std::mutex> g(m_); fn_ = &fn; pending_ = n_; ++gen_; }
         cv_.notify_all();
         std::unique_lock<std::mutex> l(m_);
         done_.wait(l, [this] { return pending_ == 0; });
+        return false;
     }
 private:
     void loop(uint32_t r) {
@@ -347,6 +349,7 @@ struct edynhip_world {
     bool stepped = false;                          // stepped since the scene was last described (set_bodies): scene-description calls are refused then
     float budget = 0.0f;                           // how much two islands of different shards may still approach before a check is due
     edynhip_world_stats stats{};
+    uint64_t paths = 0;                            // the world's own EDYNHIP_PATH_* bits (edynhip_world_debug_paths)
     std::string err;
     int fail(int code, const std::string &what) { err = what; return code; }
     // queries: the home device is devices[0]; a stream of the world's own there, the shards' answers side by side, the scan's scratch, and
@@ -379,6 +382,7 @@ void free_shard(Shard &s) {
     if (s.qisl_dev) (void)hipFree(s.qisl_dev);
     if (s.q_tot) (void)hipHostFree(s.q_tot);
     dev_free(s.q_in); dev_free(s.q_out); dev_free(s.q_ids);
+    if (s.ctx) { uint64_t m = 0; if (edynhip_debug_paths(s.ctx, &m) == EDYNHIP_OK) s.paths_gone |= m; }
     if (s.ctx) edynhip_destroy(s.ctx);
     s.ctx = nullptr; s.pack_dev = s.pack_host = nullptr; s.mon_dev = s.mon_host = nullptr;
     s.ids_dev = s.ans_dev = s.qisl_dev = nullptr; s.q_tot = nullptr; s.q_cnt = s.q_off = nullptr; s.q_boxes = nullptr;
@@ -1240,13 +1244,14 @@ int edynhip_world_step(edynhip_world *w, uint32_t nsteps) {
     if (!w) return EDYNHIP_ERR_INVALID;
     EH_TRY(ensure_built(w));
     for (uint32_t k = 0; k < nsteps; ++k) {
-        w->pool->run([w](uint32_t r) {
+        const bool on_callers_thread = w->pool->run([w](uint32_t r) {
             Shard &s = w->shards[r];
             if (s.rc != EDYNHIP_OK || s.local_ids.empty()) return;
             if (hipSetDevice(s.device) != hipSuccess) { s.rc = EDYNHIP_ERR_HIP; s.err = "hipSetDevice"; return; }
             SH_TRY(s, edynhip_step(s.ctx, 1));
             gather_shard(w, r, true);
         });
+        if (on_callers_thread) w->paths |= EDYNHIP_PATH_WORLD_SERIAL;
         EH_TRY(shard_error(w));
         ++w->stats.steps;
         w->stepped = true;
@@ -1303,6 +1308,18 @@ int edynhip_world_get_manifolds(edynhip_world *w, edynhip_manifold *out, uint32_
 int edynhip_world_get_stats(edynhip_world *w, edynhip_world_stats *out) {
     if (!w || !out) return EDYNHIP_ERR_INVALID;
     *out = w->stats;
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_debug_paths(edynhip_world *w, uint64_t *mask) {
+    if (!w || !mask) return EDYNHIP_ERR_INVALID;
+    uint64_t m = w->paths;
+    for (const Shard &s : w->shards) {
+        uint64_t sm = 0;
+        if (s.ctx && edynhip_debug_paths(s.ctx, &sm) == EDYNHIP_OK) m |= sm;
+        m |= s.paths_gone;
+    }
+    *mask = m;
     return EDYNHIP_OK;
 }
 

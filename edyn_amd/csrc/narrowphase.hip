@@ -717,6 +717,9 @@ int debug_collide(edynhip_ctx *c, uint32_t n, const int32_t *st, const float *sp
             for (const MeshDesc &md : c->host_meshes.desc) stride = std::max(stride, md.rot_size);
             const uint32_t chunk = 16384;
             const int group = (int)c->knobs.poly_group;   // (as narrowphase() below)
+            bool any_pp = false;   // only a pair of polyhedra takes the grouped routines
+            for (uint32_t i = 0; i < n && !any_pp; ++i) any_pp = st[2 * i] == EDYNHIP_SHAPE_POLYHEDRON && st[2 * i + 1] == EDYNHIP_SHAPE_POLYHEDRON;
+            if (any_pp) c->paths |= group == 0 ? EDYNHIP_PATH_POLY_ONE_LANE : group == 16 ? EDYNHIP_PATH_POLY_AXES16 : EDYNHIP_PATH_POLY_AXES8;
             float4 *scratch = nullptr;
             e = hipMalloc((void **)&scratch, (size_t)chunk * 2 * stride * sizeof(float4));
             for (uint32_t first = 0; first < n && e == hipSuccess; first += chunk) {
@@ -754,12 +757,14 @@ int narrowphase(edynhip_ctx *c) {
         uint32_t *const hints = pw + 3 * kPolyBins + 1 + 2 * cap;   // [2][cap]: one hint array per manifold array
         const PolyBins pb{pw, pw + kPolyBins, pw + 2 * kPolyBins, pw + 3 * kPolyBins, pw + 3 * kPolyBins + 1, pw + 3 * kPolyBins + 1 + cap, hints + (size_t)c->cur * cap};
         const bool use_hints = c->knobs.poly_hint;   // developer knob (A/B)
+        if (use_hints) c->paths |= EDYNHIP_PATH_POLY_HINTS;
         hipLaunchKernelGGL(k_poly_count, dim3((M + 255) / 256), dim3(256), 0, c->stream, M, c->m[c->cur], c->b, c->sleeping, pb, c->meshes, hints + (size_t)(c->cur ^ 1) * cap,
                            !c->inplace_step, use_hints);
         hipLaunchKernelGGL(k_poly_scan, dim3(1), dim3(1024), 0, c->stream, pb);
         hipLaunchKernelGGL(k_poly_scatter, dim3((M + 255) / 256), dim3(256), 0, c->stream, M, pb);
         // developer knobs (A/B): EDYNHIP_POLY_GROUP=0 the round-4 form (k_np_detect_poly for polyhedron pairs too), =8 / 16 lanes per pair in the separating-axis kernel (default 8)
         const int group = (int)c->knobs.poly_group;
+        if (group == 0) c->paths |= EDYNHIP_PATH_POLY_ONE_LANE;
         if (group != 0) {
             const uint32_t waves = 5120;   // 20 per CU of an MI355X (the axes kernel runs five per SIMD): the grids stride over the pairs
             const int group2 = (int)c->knobs.poly_group2;   // lanes per surviving pair: 4 (default: 16 pairs per wave), 8 or 16
@@ -771,16 +776,16 @@ int narrowphase(edynhip_ctx *c) {
             unsigned long long *const pd = prof ? prof_dev : nullptr;
             // (measured and dropped: the contact kernel compiled for three waves per SIMD - 168 VGPRs and 260 B of spills - 324 -> 304 steps/s on polyheap32k)
             if (prof) {
-                if (group == 16) hipLaunchKernelGGL((k_np_pp_axes<16, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                else hipLaunchKernelGGL((k_np_pp_axes<8, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                if (group2 == 8) hipLaunchKernelGGL((k_np_pp_contacts<8, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                else hipLaunchKernelGGL((k_np_pp_contacts<4, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
+                if (group == 16) { c->paths |= EDYNHIP_PATH_POLY_AXES16; hipLaunchKernelGGL((k_np_pp_axes<16, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                else { c->paths |= EDYNHIP_PATH_POLY_AXES8; hipLaunchKernelGGL((k_np_pp_axes<8, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                if (group2 == 8) { c->paths |= EDYNHIP_PATH_POLY_CONTACTS8; hipLaunchKernelGGL((k_np_pp_contacts<8, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                else { c->paths |= EDYNHIP_PATH_POLY_CONTACTS4; hipLaunchKernelGGL((k_np_pp_contacts<4, true>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
             } else {
-                if (group == 16) hipLaunchKernelGGL((k_np_pp_axes<16, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                else hipLaunchKernelGGL((k_np_pp_axes<8, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                if (group2 == 8) hipLaunchKernelGGL((k_np_pp_contacts<8, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                else if (group2 == 16) hipLaunchKernelGGL((k_np_pp_contacts<16, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
-                else hipLaunchKernelGGL((k_np_pp_contacts<4, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd);
+                if (group == 16) { c->paths |= EDYNHIP_PATH_POLY_AXES16; hipLaunchKernelGGL((k_np_pp_axes<16, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                else { c->paths |= EDYNHIP_PATH_POLY_AXES8; hipLaunchKernelGGL((k_np_pp_axes<8, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                if (group2 == 8) { c->paths |= EDYNHIP_PATH_POLY_CONTACTS8; hipLaunchKernelGGL((k_np_pp_contacts<8, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                else if (group2 == 16) { c->paths |= EDYNHIP_PATH_POLY_CONTACTS16; hipLaunchKernelGGL((k_np_pp_contacts<16, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
+                else { c->paths |= EDYNHIP_PATH_POLY_CONTACTS4; hipLaunchKernelGGL((k_np_pp_contacts<4, false>), dim3(waves), dim3(64), 0, c->stream, mfc, c->b, st, c->meshes, pb, pd); }
             }
             if (prof && ++prof_calls % 100 == 0) {
                 unsigned long long h[16];

@@ -2987,6 +2987,8 @@ static int launch_velocity(edynhip_ctx *c, SolvePlan &p, uint32_t *launches) {
         // hand-off polling relies on
         if (launch_resident(c, df_velocity_fn(p.lanes, p.fused_rows), grid, 64, params) == hipSuccess) {
             ++*launches;
+            c->paths |= (p.lanes == 4u ? EDYNHIP_PATH_VEL_LANES4 : p.lanes == 2u ? EDYNHIP_PATH_VEL_LANES2 : EDYNHIP_PATH_VEL_LANES1) | (a.xcd_lists ? EDYNHIP_PATH_VEL_XCD : 0u) |
+                        (na > a.stride ? EDYNHIP_PATH_VEL_MULTI_ROUND : 0u) | (p.lanes == 2u && a.nap != 1u ? EDYNHIP_PATH_VEL_NAP : 0u);   // (only k_contact_solve_df2 reads the nap)
         } else {   // e.g. the device is shared and cannot hold the grid: use the per-colour schedule from now on
             (void)hipGetLastError();
             c->df_mode = 0;
@@ -3001,11 +3003,13 @@ static int launch_velocity(edynhip_ctx *c, SolvePlan &p, uint32_t *launches) {
         EH_TRY(trace.end(c, kn.df_trace, p.lanes != 0, na, a.stride, a.sweeps, per_wave));
     }
     if ((!p.lanes && p.isl_fused) || (p.lanes && p.mixed)) {   // mixed: the islands with joints, beside the dataflow launch
+        c->paths |= p.lanes ? EDYNHIP_PATH_MIXED : EDYNHIP_PATH_ISLAND_FUSED;
         const IslSolveArgs isl_args = island_args(c, p, c->cfg.num_velocity_iterations);
         if (p.fused_rows) hipLaunchKernelGGL(k_island_velocity<true>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
         else hipLaunchKernelGGL(k_island_velocity<false>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
         ++*launches;
     } else if (!p.lanes) {
+        if (p.na + c->j.n) c->paths |= EDYNHIP_PATH_PER_COLOUR;
         joints_pass(c, true, launches);
         contacts_pass(c, p, true, launches);
         for (uint32_t it = 0; it < c->cfg.num_velocity_iterations; ++it) {
@@ -3062,6 +3066,7 @@ static int launch_position(edynhip_ctx *c, const SolvePlan &p, const float4 **fi
                 c->df_mode = 0;
                 break;
             }
+            c->paths |= (xcd_lists ? EDYNHIP_PATH_POS_XCD : 0u) | (na > a.stride ? EDYNHIP_PATH_POS_MULTI_ROUND : 0u);
         }
         EH_TRY(trace.end(c, kn.dfp_trace, true, na, grid * 32u, P, 32u));
         // the bodies' transforms live in the hand-off slots while the dataflow launches run; k_finish picks them up
@@ -3082,7 +3087,10 @@ static int launch_position(edynhip_ctx *c, const SolvePlan &p, const float4 **fi
         if (p.isl_fused) {
             const IslSolveArgs isl_args = island_args(c, p, P);
             hipLaunchKernelGGL(block_pos ? k_island_position<true> : k_island_position<false>, dim3(kIslGrid), dim3(64), 0, s, isl_args);
-        } else pos_per_colour(c, p, 0);
+        } else {
+            if (p.push) c->paths |= EDYNHIP_PATH_POS_COLOUR_PUSH;
+            pos_per_colour(c, p, 0);
+        }
     }
     return EDYNHIP_OK;
 }

@@ -152,6 +152,12 @@ class MultiWorld:
         self._check(self._L.edynhip_world_query_aabb_device(self._h, cat, int(n), C.c_void_p(boxes_ptr), flags, C.c_void_p(offsets_ptr),
                                                             C.c_void_p(ids_ptr) if ids_ptr else None, int(capacity), C.c_void_p(total_ptr)))
 
+    def debug_paths(self):
+        """World.debug_paths over every shard the world has had, plus "WORLD_SERIAL" (edynhip_world_debug_paths)."""
+        mask = C.c_uint64(0)
+        self._check(self._L.edynhip_world_debug_paths(self._h, C.byref(mask)))
+        return {name for name, bit in _capi.PATH_BITS.items() if mask.value & bit}
+
     def get_stats(self):
         st = _capi.WorldStats()
         self._check(self._L.edynhip_world_get_stats(self._h, C.byref(st)))

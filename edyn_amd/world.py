@@ -592,6 +592,15 @@ class World:
         self._check(self._L.edynhip_debug_collide(self._h, n, _ptr(st), _ptr(sp), _ptr(ps), _ptr(qs), threshold, _ptr(out), _ptr(cnt)))
         return out, cnt
 
+    def debug_paths(self):
+        """Which alternative code paths this context has taken since it was created: the set of names of _capi.PATH_BITS
+        (edynhip_debug_paths; a world that has no context yet has taken none)."""
+        if self._h is None:
+            return set()
+        mask = C.c_uint64(0)
+        self._check(self._L.edynhip_debug_paths(self._h, C.byref(mask)))
+        return {name for name, bit in _capi.PATH_BITS.items() if mask.value & bit}
+
     def set_joint_warm_start(self, impulses24, angles=None):
         """Applied impulses ([nj, 24], the layout of get_joint_impulses24) and tracked angles of the joints, by caller index: what a
         world carries into another (edynhip_set_joint_warm_start)."""

@@ -479,6 +479,45 @@ int edynhip_prefetched_events(edynhip_ctx *ctx, const edynhip_contact_event **ev
 int edynhip_debug_collide(edynhip_ctx *ctx, uint32_t n, const int32_t *shape_type, const float *shape_param, const float *pos,
                           const float *orn, float threshold, float *out_points, uint32_t *out_count);
 
+/* Test hook (additive to ABI 15): which of the library's alternative code paths this context has taken. *mask = the OR, since the context
+ * was created, of one bit per HOST-side branch actually taken - set at the branch itself, once the launch it selects was accepted - so a parity
+ * test that switches a path on through a development knob (scripts/README.md) or through the scene's size can show that the path ran.
+ * No kernel reads or writes it. Replaces nothing in the reference. */
+#define EDYNHIP_PATH_COMPACT_DIRECT     (1ull << 0)   /* pair compaction: k_bp_compact<true>, its own scan */
+#define EDYNHIP_PATH_COMPACT_LIBRARY    (1ull << 1)   /* pair compaction: scan_u32 + k_bp_compact<false> */
+#define EDYNHIP_PATH_SORT_DIRECT        (1ull << 2)   /* colour sort: k_cs_hist<true> + k_cs_scatter<true> */
+#define EDYNHIP_PATH_SORT_LIBRARY       (1ull << 3)   /* colour sort: k_cs_hist<false> + scan_u32 + k_cs_scatter<false> + k_col_offsets */
+#define EDYNHIP_PATH_SPECULATE          (1ull << 4)   /* the manifold build was launched before the pair count reached the host */
+#define EDYNHIP_PATH_INPLACE            (1ull << 5)   /* a step kept the previous step's manifold array (unchanged pair set) */
+#define EDYNHIP_PATH_LISTS_FORCED       (1ull << 6)   /* the tree was walked in a step in which the candidate lists were still valid (EDYNHIP_BP_LISTS=0) */
+#define EDYNHIP_PATH_LOOKAHEAD_CHANGED  (1ull << 7)   /* the candidate lists' look-ahead was halved or doubled */
+#define EDYNHIP_PATH_RELABEL_COMPRESS0  (1ull << 8)   /* a step found its label certificate broken and relabelled the islands in full (the forced relabel after a scene edit does not count), with no pointer-jumping pass */
+#define EDYNHIP_PATH_RELABEL_COMPRESS1  (1ull << 9)   /*   ... with one */
+#define EDYNHIP_PATH_RELABEL_COMPRESSN  (1ull << 10)  /*   ... with more than one */
+#define EDYNHIP_PATH_VEL_XCD            (1ull << 11)  /* dataflow velocity launch with XCD-local task lists */
+#define EDYNHIP_PATH_POS_XCD            (1ull << 12)  /* dataflow position launch with XCD-local task lists */
+#define EDYNHIP_PATH_VEL_LANES1         (1ull << 13)  /* k_contact_solve_df */
+#define EDYNHIP_PATH_VEL_LANES2         (1ull << 14)  /* k_contact_solve_df2 */
+#define EDYNHIP_PATH_VEL_LANES4         (1ull << 15)  /* k_contact_solve_df4 */
+#define EDYNHIP_PATH_VEL_MULTI_ROUND    (1ull << 16)  /* a dataflow velocity launch whose waves take more than one task per sweep */
+#define EDYNHIP_PATH_POS_MULTI_ROUND    (1ull << 17)  /* the same for a dataflow position launch */
+#define EDYNHIP_PATH_POS_COLOUR_PUSH    (1ull << 18)  /* position solve per colour behind a dataflow (push) velocity solve */
+#define EDYNHIP_PATH_MIXED              (1ull << 19)  /* mixed schedule */
+#define EDYNHIP_PATH_ISLAND_FUSED       (1ull << 20)  /* island-fused schedule */
+#define EDYNHIP_PATH_PER_COLOUR         (1ull << 21)  /* velocity solve per colour */
+#define EDYNHIP_PATH_POLY_ONE_LANE      (1ull << 22)  /* polyhedron pairs: one lane per pair in k_np_detect_poly */
+#define EDYNHIP_PATH_POLY_AXES8         (1ull << 23)  /* k_np_pp_axes<8> */
+#define EDYNHIP_PATH_POLY_AXES16        (1ull << 24)  /* k_np_pp_axes<16> */
+#define EDYNHIP_PATH_POLY_CONTACTS4     (1ull << 25)  /* k_np_pp_contacts<4> */
+#define EDYNHIP_PATH_POLY_CONTACTS8     (1ull << 26)  /* k_np_pp_contacts<8> */
+#define EDYNHIP_PATH_POLY_CONTACTS16    (1ull << 27)  /* k_np_pp_contacts<16> */
+#define EDYNHIP_PATH_POLY_HINTS         (1ull << 28)  /* separating-axis hints used */
+#define EDYNHIP_PATH_RECORDS_DIRECT     (1ull << 29)  /* edynhip_snapshot_records packed straight into the pinned slot */
+#define EDYNHIP_PATH_RECORDS_COPY       (1ull << 30)  /* ... through a device block and the copy engine */
+#define EDYNHIP_PATH_WORLD_SERIAL       (1ull << 31)  /* multi-device world only: the shards were stepped on the caller's thread */
+#define EDYNHIP_PATH_VEL_NAP            (1ull << 32)  /* k_contact_solve_df2 launched with a pause between polls other than the default (EDYNHIP_DF_NAP) */
+int edynhip_debug_paths(edynhip_ctx *ctx, uint64_t *mask);
+
 /* Island sleeping (EDYNHIP_FLAG_SLEEPING): asleep[n] = 1 where the body carries sleeping_tag; wake_all = wake_up_entity on
  * everything (also implied by edynhip_set_state). island_manager.cpp:541-565, util/island_util.cpp:61-66. */
 int edynhip_get_asleep(edynhip_ctx *ctx, uint8_t *asleep);
@@ -507,6 +546,9 @@ int edynhip_set_asleep(edynhip_ctx *ctx, const uint8_t *asleep);
 int edynhip_get_sleep_timers(edynhip_ctx *ctx, uint32_t *island_label, double *since, double *clock);
 int edynhip_set_sleep_timers(edynhip_ctx *ctx, const uint32_t *island_label, const double *since, double clock);
 
+/* The version changes when a caller built against the previous header would misbehave: a struct's layout or size, a function's signature,
+ * the meaning of an argument, a flag or a result. A new entry point beside the existing ones ("additive to ABI n" where it is declared)
+ * leaves it alone: nothing an older caller uses has moved, and a newer caller looks the symbol up. */
 uint32_t edynhip_abi_version(void);
 
 /* polyhedron_shape's convex_mesh (include/edyn/shapes/convex_mesh.hpp:17-70): vertices[num_vertices][3], the faces' vertex indices
@@ -608,6 +650,9 @@ int edynhip_world_query_aabb(edynhip_world *w, int category, uint32_t n, const f
                           uint32_t *offsets, uint32_t *ids, uint32_t capacity, uint32_t *total);
 int edynhip_world_query_aabb_device(edynhip_world *w, int category, uint32_t n, const void *boxes_f4, uint32_t flags,
                           void *offsets, void *ids, uint32_t capacity, void *total);
+/* edynhip_debug_paths of a multi-device world (additive to ABI 15): the OR over every shard context the world has had, plus
+ * EDYNHIP_PATH_WORLD_SERIAL when the shards were stepped one after the other on the caller's thread. */
+int edynhip_world_debug_paths(edynhip_world *w, uint64_t *mask);
 
 /* The pieces of the above that processes owning ONE GPU each use (edyn_amd/parallel.py ShardedWorld over torch.distributed / RCCL):
  * the island partitioner - longest-processing-time-first over the summed weights, deterministic (islands by descending weight, ties
