@@ -130,6 +130,7 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_raycast", "edynhip_raycast_device",
            "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats",
            "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device",
+           "edynhip_world_get_contact_events", "edynhip_world_get_point_ids",
            "edynhip_debug_paths", "edynhip_world_debug_paths"]
 
 _lib = None
@@ -239,6 +240,8 @@ def lib():
                                                C.POINTER(C.c_uint32)]
         L.edynhip_world_query_aabb_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                       C.c_void_p]
+        L.edynhip_world_get_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.edynhip_world_get_point_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_partition_islands.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_island_boxes_overlap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_get_island_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]

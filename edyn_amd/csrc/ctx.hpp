@@ -115,7 +115,7 @@ __device__ __forceinline__ const float *mix_lookup(const Bodies &b, uint32_t bod
 
 // Contact events (EDYNHIP_FLAG_CONTACT_EVENTS; edynhip.h edynhip_contact_event has the same layout).
 struct ContactEvent { uint32_t type, step, bodyA, bodyB; uint64_t pid; };
-struct EventSink { ContactEvent *buf; uint32_t *count; uint32_t cap; uint32_t step; };   // buf == nullptr: events are off
+struct EventSink { ContactEvent *buf; uint32_t *count; uint32_t cap; uint32_t step; uint32_t tag; };   // buf == nullptr: events are off; tag: ORed into the low word of every id issued (edynhip_ctx::event_id_tag)
 __device__ __forceinline__ void emit_event(const EventSink &ev, uint32_t type, uint32_t a, uint32_t b, uint64_t pid) {
     const uint32_t i = atomicAdd(ev.count, 1u);   // may run past cap: the host reports the overflow
     if (i < ev.cap) ev.buf[i] = ContactEvent{type, ev.step, a, b, pid};
@@ -491,6 +491,10 @@ struct edynhip_ctx {
     const uint32_t *answers = nullptr;
     std::vector<uint32_t> host_answers;
     const uint32_t *query_island = nullptr;
+    // Contact events of a shard (multi.hip build_shard; both 0 on a context of its own): events carry event_step_base + step_index - the
+    // world's step count, which goes on where a re-partition restarts step_index - and every point id issued here has event_id_tag (the
+    // shard, above the manifold index: kEventTagShift) in its low word, so that ids of different shards never collide.
+    uint32_t event_step_base = 0, event_id_tag = 0;
 };
 
 namespace eh {
@@ -509,7 +513,7 @@ int islands(edynhip_ctx *c);
 // first counter publish is enqueued and before the host waits for it; *first_final: those counters were the final ones.
 int colour_contacts(edynhip_ctx *c, const std::function<void()> &between, bool *first_final);
 Knobs read_knobs();   // capi.hip: the only function that reads EDYNHIP_* variables
-inline EventSink event_sink(const edynhip_ctx *c) { return EventSink{c->events, c->event_count, c->event_cap, c->step_index}; }
+inline EventSink event_sink(const edynhip_ctx *c) { return EventSink{c->events, c->event_count, c->event_cap, c->event_step_base + c->step_index, c->event_id_tag}; }
 int restitution(edynhip_ctx *c);   // restitution.hip: solve_restitution, before gravity and the constraint solver (solver.cpp:397)
 int solve(edynhip_ctx *c);
 int refresh_derived(edynhip_ctx *c);
@@ -534,6 +538,13 @@ int shard_raycast(edynhip_ctx *c, uint32_t n, const void *p0_f4, const void *p1_
 // fill pass of the queries counted last (ids[capacity] on this device)
 int shard_query_count(edynhip_ctx *c, int category, uint32_t n, const void *boxes_f4, uint32_t flags, const uint32_t **cnt, const uint32_t **offsets, const unsigned long long **tot64);
 int shard_query_fill(edynhip_ctx *c, int category, uint32_t n, const void *boxes_f4, uint32_t flags, uint32_t *ids, uint32_t capacity);
+// world_events.hip: the events of the last step call (`expected` of them: the count the caller has already read; the kernel bounds itself by
+// the device counter) with global body indices into out[event_cap]; the current manifold array's point ids as ids[num_manifolds][4]
+// (edynhip_get_point_ids' table, on the device), and the same table written back over the ids edynhip_set_manifolds issued
+constexpr uint32_t kEventTagShift = 28, kEventTagShards = 16;   // id low word: shard << 28 | manifold index << 2 | slot
+int shard_translate_events(edynhip_ctx *c, uint32_t expected, const uint32_t *local_ids_dev, uint32_t n_local, void *out);
+int shard_gather_point_ids(edynhip_ctx *c, uint64_t *ids_dev);
+int shard_inject_point_ids(edynhip_ctx *c, const uint64_t *ids_dev, uint32_t num_manifolds);
 }  // namespace eh
 
 #define EH_HIP(c, call)                                                          \

@@ -31,6 +31,7 @@
 #include <mutex>
 #include <numeric>
 #include <thread>
+#include <unordered_map>
 
 namespace eh {
 
@@ -274,6 +275,11 @@ struct Shard {
     const void *q_boxes = nullptr;
     const uint32_t *q_cnt = nullptr, *q_off = nullptr;
     unsigned long long *q_tot = nullptr;
+    // contact events (EDYNHIP_FLAG_CONTACT_EVENTS only): the last step's event count, fetched with the state (pinned), and how many of them
+    // the shard holds; the step's events in global indices (device, [event_cap]); the point ids of `manifolds` as [m][4], device and host
+    uint32_t *ev_cnt_host = nullptr, ev_held = 0;
+    DevBuf ev_out, pid_buf;
+    std::vector<uint64_t> pids;
 };
 
 class Pool {   // one persistent host thread per shard (a context is single-threaded; its step spins on its own counters)
@@ -359,6 +365,12 @@ struct edynhip_world {
     unsigned long long *q_pin = nullptr;           // pinned: the 64-bit total of the last count
     std::vector<uint32_t> query_labels;            // island labels (global) of the state the shards were last rebuilt from
     std::vector<float4> q_stage;
+    // contact events (EDYNHIP_FLAG_CONTACT_EVENTS only): the events of the last edynhip_world_step call, global indices, on the home device -
+    // every step appends every shard's block -, whether a shard's own list overflowed in that call, and the steps since the scene was described
+    DevBuf ev_list;
+    uint32_t ev_n = 0, step_count = 0;
+    bool ev_overflow = false;
+    bool events_on() const { return (cfg.flags & EDYNHIP_FLAG_CONTACT_EVENTS) != 0; }
 };
 
 namespace {
@@ -369,6 +381,7 @@ int shard_error(edynhip_world *w) {
     return EDYNHIP_OK;
 }
 #define SH_TRY(s, expr) do { int r__ = (expr); if (r__ != EDYNHIP_OK) { (s).rc = r__; (s).err = (s).ctx ? edynhip_last_error((s).ctx) : edynhip_last_error(nullptr); return; } } while (0)
+#define W_HIP(w, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return (w)->fail(EDYNHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
 #define SH_HIP(s, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { (s).rc = EDYNHIP_ERR_HIP; (s).err = std::string(#call) + ": " + hipGetErrorString(e__); return; } } while (0)
 
 void free_shard(Shard &s) {
@@ -382,6 +395,9 @@ void free_shard(Shard &s) {
     if (s.qisl_dev) (void)hipFree(s.qisl_dev);
     if (s.q_tot) (void)hipHostFree(s.q_tot);
     dev_free(s.q_in); dev_free(s.q_out); dev_free(s.q_ids);
+    if (s.ev_cnt_host) (void)hipHostFree(s.ev_cnt_host);
+    dev_free(s.ev_out); dev_free(s.pid_buf);
+    s.ev_cnt_host = nullptr; s.ev_held = 0;
     if (s.ctx) { uint64_t m = 0; if (edynhip_debug_paths(s.ctx, &m) == EDYNHIP_OK) s.paths_gone |= m; }
     if (s.ctx) edynhip_destroy(s.ctx);
     s.ctx = nullptr; s.pack_dev = s.pack_host = nullptr; s.mon_dev = s.mon_host = nullptr;
@@ -424,6 +440,9 @@ struct Carry {   // what travels with the islands through a re-partition (global
     // (thousands) instead of every body's box (hundreds of thousands)
     std::vector<IslandBox> island_boxes;
     std::vector<uint32_t> island;              // per global body: its island label at the re-partition (what the island query reports until the next step)
+    // contact events: the ids of the carried points by body pair (body[0] << 32 | body[1], global) - a rebuilt shard puts them back over the
+    // ids edynhip_set_manifolds issues, so a point keeps its id whichever shards it lives on
+    std::unordered_map<uint64_t, std::array<uint64_t, 4>> point_ids;
 };
 
 int shard_filter_thunk(void *user, uint32_t body, uint32_t other) {
@@ -500,6 +519,18 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     } else {
         SH_TRY(s, edynhip_synchronize(s.ctx));
     }
+    if (w->events_on()) {
+        // World point ids: (world step of creation + 1) << 32 | shard << 28 | manifold index << 2 | slot. The context counts the world's steps
+        // (its own step_index restarts with edynhip_set_bodies below) and tags the ids it issues, so events and ids are in world terms natively.
+        if (r >= kEventTagShards || s.ctx->m[0].cap > (1u << (kEventTagShift - 2))) {
+            s.rc = EDYNHIP_ERR_CAPACITY; s.err = "contact events on a multi-device world: at most 16 shards of at most 2^26 manifolds each";
+            return;
+        }
+        s.ctx->event_step_base = w->step_count; s.ctx->event_id_tag = r << kEventTagShift;
+        if (!s.ev_cnt_host) SH_HIP(s, hipHostMalloc((void **)&s.ev_cnt_host, sizeof(uint32_t), hipHostMallocDefault));
+        *s.ev_cnt_host = 0; s.ev_held = 0;
+        SH_HIP(s, dev_grow(s.ev_out, (size_t)std::max<uint32_t>(s.ctx->event_cap, 1) * sizeof(ContactEvent)));
+    }
     // bodies: the scene's definitions with the CURRENT state
     const std::vector<float> &P = from_state ? w->pos : sc.pos, &Q = from_state ? w->orn : sc.orn, &V = from_state ? w->linvel : sc.linvel, &W = from_state ? w->angvel : sc.angvel;
     auto kind = take(sc.kind, s.local_ids, 1), shape_type = take(sc.shape_type, s.local_ids, 1);
@@ -548,17 +579,31 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     if (w->filter) SH_TRY(s, edynhip_set_pair_filter(s.ctx, &shard_filter_thunk, &w->shard_filters[r]));
     if (carry.any) {
         std::vector<edynhip_manifold> mine;
-        if (!carry.per_shard.empty()) {
-            mine.swap(carry.per_shard[r]);
-            for (edynhip_manifold &m : mine) { m.body[0] = (uint32_t)s.to_local[m.body[0]]; m.body[1] = (uint32_t)s.to_local[m.body[1]]; }
-        } else
-        for (const edynhip_manifold &m : carry.manifolds)
-            if (w->rank_of[m.body[0]] == (int32_t)r || w->rank_of[m.body[1]] == (int32_t)r) {
-                mine.push_back(m);
-                mine.back().body[0] = (uint32_t)s.to_local[m.body[0]]; mine.back().body[1] = (uint32_t)s.to_local[m.body[1]];   // a monotone map: the canonical order is kept
+        if (!carry.per_shard.empty()) mine.swap(carry.per_shard[r]);
+        else
+            for (const edynhip_manifold &m : carry.manifolds)
+                if (w->rank_of[m.body[0]] == (int32_t)r || w->rank_of[m.body[1]] == (int32_t)r) mine.push_back(m);
+        std::vector<uint64_t> mine_ids;   // contact events: the carried points keep their ids
+        if (w->events_on() && !mine.empty()) {
+            mine_ids.resize(4 * mine.size());
+            for (size_t k = 0; k < mine.size(); ++k) {
+                const auto it = carry.point_ids.find(((uint64_t)mine[k].body[0] << 32) | mine[k].body[1]);
+                if (it == carry.point_ids.end()) {
+                    s.rc = EDYNHIP_ERR_INTERNAL; s.err = "a carried manifold (bodies " + std::to_string(mine[k].body[0]) + ", " + std::to_string(mine[k].body[1]) + ") has no point ids";
+                    return;
+                }
+                std::memcpy(&mine_ids[4 * k], it->second.data(), 4 * sizeof(uint64_t));
             }
+        }
+        for (edynhip_manifold &m : mine) { m.body[0] = (uint32_t)s.to_local[m.body[0]]; m.body[1] = (uint32_t)s.to_local[m.body[1]]; }   // a monotone map: the canonical order is kept
         trace.mark("joints, exclusions, select carried manifolds");
         if (!mine.empty()) SH_TRY(s, edynhip_set_manifolds(s.ctx, mine.data(), (uint32_t)mine.size()));
+        if (!mine_ids.empty()) {
+            SH_HIP(s, dev_grow(s.pid_buf, mine_ids.size() * sizeof(uint64_t)));
+            SH_HIP(s, hipMemcpyAsync(s.pid_buf.p, mine_ids.data(), mine_ids.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s.ctx->stream));
+            SH_TRY(s, shard_inject_point_ids(s.ctx, (const uint64_t *)s.pid_buf.p, (uint32_t)mine.size()));
+            SH_HIP(s, hipStreamSynchronize(s.ctx->stream));   // (mine_ids is read by the copy until here)
+        }
         trace.mark("edynhip_set_manifolds");
         if (njl && !carry.imp24.empty()) {
             auto i24 = take(carry.imp24, s.local_joints, 24), ang = take(carry.angle, s.local_joints, 1);
@@ -641,8 +686,55 @@ void gather_shard(edynhip_world *w, uint32_t r, bool with_growth) {
     SH_TRY(s, edynhip_pack_state_device(s.ctx, s.pack_dev, 0, nl));
     SH_HIP(s, hipMemcpyAsync(s.pack_host, s.pack_dev, (size_t)nl * 13 * sizeof(float), hipMemcpyDeviceToHost, st));
     SH_HIP(s, hipMemcpyAsync(s.mon_host, s.mon_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    const bool events = with_growth && s.ctx->events && s.ev_cnt_host;   // (with_growth: after a step)
+    if (events) SH_HIP(s, hipMemcpyAsync(s.ev_cnt_host, s.ctx->event_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SH_HIP(s, hipStreamSynchronize(st));
     scatter_state(w, s);
+    if (events) {   // the step's events in global indices, enqueued behind the step: the world appends the block to its list (append_events)
+        s.ev_held = std::min(*s.ev_cnt_host, s.ctx->event_cap);
+        SH_TRY(s, shard_translate_events(s.ctx, s.ev_held, s.ids_dev, nl, s.ev_out.p));
+    }
+}
+
+// After a step of every shard: the shards' translated blocks go to the end of the world's list on the home device, device to device, each
+// on its shard's stream (behind the translation; the next step of that shard queues up behind the copy). The offsets follow from the
+// counts the shards fetched with their state.
+int append_events(edynhip_world *w) {
+    size_t total = 0;
+    for (Shard &s : w->shards) {
+        if (s.local_ids.empty() || !s.ctx || !s.ev_cnt_host) { s.ev_held = 0; continue; }
+        if (*s.ev_cnt_host > s.ctx->event_cap) w->ev_overflow = true;
+        total += s.ev_held;
+    }
+    if (total == 0) return EDYNHIP_OK;
+    const int home = w->devices[0];
+    const size_t need = ((size_t)w->ev_n + total) * sizeof(ContactEvent);
+    if ((size_t)w->ev_n + total > 0xFFFFFFFFull) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_step: more than 2^32 - 1 contact events in one call");
+    if (need > w->ev_list.cap) {   // grow and keep what the earlier steps of this call appended (copies of theirs may still be in flight)
+        for (Shard &s : w->shards) if (s.ctx) { W_HIP(w, hipSetDevice(s.device)); W_HIP(w, hipStreamSynchronize(s.ctx->stream)); }
+        W_HIP(w, hipSetDevice(home));
+        DevBuf bigger;
+        W_HIP(w, dev_grow(bigger, std::max(std::max(need, 2 * w->ev_list.cap), (size_t)4096 * sizeof(ContactEvent))));
+        if (w->ev_n) {
+            const hipError_t e = hipMemcpy(bigger.p, w->ev_list.p, (size_t)w->ev_n * sizeof(ContactEvent), hipMemcpyDeviceToDevice);
+            if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess) { dev_free(bigger); return w->fail(EDYNHIP_ERR_HIP, "edynhip_world_step: growing the event list"); }
+        }
+        dev_free(w->ev_list);
+        w->ev_list = bigger;
+    }
+    size_t at = w->ev_n;
+    for (Shard &s : w->shards) {
+        if (s.ev_held == 0) continue;
+        uint8_t *dst = (uint8_t *)w->ev_list.p + at * sizeof(ContactEvent);
+        const size_t bytes = (size_t)s.ev_held * sizeof(ContactEvent);
+        W_HIP(w, hipSetDevice(s.device));
+        if (s.device == home) W_HIP(w, hipMemcpyAsync(dst, s.ev_out.p, bytes, hipMemcpyDeviceToDevice, s.ctx->stream));
+        else W_HIP(w, hipMemcpyPeerAsync(dst, home, s.ev_out.p, s.device, bytes, s.ctx->stream));
+        at += s.ev_held;
+        s.ev_held = 0;
+    }
+    w->ev_n = (uint32_t)at;
+    return EDYNHIP_OK;
 }
 
 // island boxes of shard r, reduced on its device; also records the AABBs the growth is measured against and clears the growth.
@@ -711,7 +803,7 @@ void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy) {
     if (s.rc != EDYNHIP_OK) return;
     const uint32_t nl = (uint32_t)s.local_ids.size();
     if (light) { s.labels.assign(nl, 0); s.aabb.assign((size_t)nl * 6, 0.f); s.asleep.assign(nl, 0); }
-    s.manifolds.clear(); s.imp24.clear(); s.imp10.clear();
+    s.manifolds.clear(); s.imp24.clear(); s.imp10.clear(); s.pids.clear();
     if (nl == 0) return;
     SH_HIP(s, hipSetDevice(s.device));
     if (light) {
@@ -728,6 +820,13 @@ void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy) {
     s.manifolds.resize(nm);
     if (nm) SH_TRY(s, edynhip_get_manifolds(s.ctx, s.manifolds.data(), nm, &nm));
     s.manifolds.resize(nm);
+    if (nm && s.ctx->events) {   // contact events: the points' ids travel with the records, [m][4] in the same order
+        s.pids.resize(4 * (size_t)nm);
+        SH_HIP(s, dev_grow(s.pid_buf, s.pids.size() * sizeof(uint64_t)));
+        SH_TRY(s, shard_gather_point_ids(s.ctx, (uint64_t *)s.pid_buf.p));
+        SH_HIP(s, hipMemcpyAsync(s.pids.data(), s.pid_buf.p, s.pids.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s.ctx->stream));
+        SH_HIP(s, hipStreamSynchronize(s.ctx->stream));
+    }
     const uint32_t njl = (uint32_t)s.local_joints.size();
     if (njl) {
         s.imp24.assign((size_t)njl * 24, 0.f); s.imp10.assign((size_t)njl * 10, 0.f);
@@ -742,15 +841,17 @@ inline uint64_t canonical_key(const HostScene &sc, uint32_t a, uint32_t b) {   /
     return ((uint64_t)owner << 32) | other;
 }
 
-// gathers the manifolds of all shards, each once, global indices, canonical order
-void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out) {
+// gathers the manifolds of all shards, each once, global indices, canonical order; ids (or nullptr): their points' ids [m][4], in that order
+void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::vector<uint64_t> *ids = nullptr) {
     out.clear();
+    std::vector<const uint64_t *> from;   // per gathered record: its row of the shard's id table
     for (uint32_t r = 0; r < w->shards.size(); ++r) {
         Shard &s = w->shards[r];
-        for (edynhip_manifold m : s.manifolds) {
+        for (size_t k = 0; k < s.manifolds.size(); ++k) {
+            edynhip_manifold m = s.manifolds[k];
             m.body[0] = s.local_ids[m.body[0]]; m.body[1] = s.local_ids[m.body[1]];
             const int32_t ra = w->rank_of[m.body[0]], rb = w->rank_of[m.body[1]];
-            if (ra == (int32_t)r || (ra < 0 && rb == (int32_t)r)) out.push_back(m);
+            if (ra == (int32_t)r || (ra < 0 && rb == (int32_t)r)) { out.push_back(m); if (ids) from.push_back(s.pids.size() == 4 * s.manifolds.size() ? &s.pids[4 * k] : nullptr); }
         }
     }
     // canonical order: sort (key, position) pairs and move every 336-byte record once (a stable sort of the records themselves, with
@@ -761,6 +862,21 @@ void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out) {
     std::vector<edynhip_manifold> sorted(out.size());
     for (uint32_t k = 0; k < out.size(); ++k) sorted[k] = out[order[k].second];
     out.swap(sorted);
+    if (ids) {
+        ids->assign(4 * out.size(), 0);
+        for (uint32_t k = 0; k < out.size(); ++k) if (const uint64_t *row = from[order[k].second]) std::memcpy(&(*ids)[4 * (size_t)k], row, 4 * sizeof(uint64_t));
+    }
+}
+
+// contact events: the ids of a collected shard's points go with the re-partition, by global body pair (before s.manifolds is taken apart)
+void carry_point_ids(const Shard &s, Carry &carry) {
+    if (s.pids.size() != 4 * s.manifolds.size()) return;
+    for (size_t k = 0; k < s.manifolds.size(); ++k) {
+        const edynhip_manifold &m = s.manifolds[k];
+        std::array<uint64_t, 4> row;
+        std::memcpy(row.data(), &s.pids[4 * k], sizeof(row));
+        carry.point_ids[((uint64_t)s.local_ids[m.body[0]] << 32) | s.local_ids[m.body[1]]] = row;
+    }
 }
 
 // `only` (or nullptr = all): the shards to build; the others keep their contexts - their bodies, and therefore their local indices, are unchanged.
@@ -832,6 +948,7 @@ int repartition(edynhip_world *w, bool sticky) {
         for (uint32_t r = 0; r < W; ++r) {
             Shard &s = w->shards[r];
             if (only && !(*only)[r]) { s.manifolds.clear(); continue; }
+            carry_point_ids(s, carry);
             for (const edynhip_manifold &m : s.manifolds) {   // weight = 1 + the contact points the body takes part in (balance the rows)
                 const uint32_t a = s.local_ids[m.body[0]], b = s.local_ids[m.body[1]];
                 if (w->rank_of[a] == (int32_t)r) weights[a] += m.num_points;
@@ -931,6 +1048,7 @@ int repartition(edynhip_world *w, bool sticky) {
     w->pool->run([w, &changed](uint32_t r) { if (changed[r]) collect_shard(w, r, false, true); });
     EH_TRY(shard_error(w));
     trace.mark("collect manifolds / joint impulses of the changed shards");
+    for (uint32_t r = 0; r < W; ++r) if (changed[r]) carry_point_ids(w->shards[r], carry);
     // joints' applied impulses and angles of the changed shards
     for (uint32_t r = 0; r < W; ++r) {
         Shard &s = w->shards[r];
@@ -1144,7 +1262,7 @@ void edynhip_world_destroy(edynhip_world *w) {
     for (Shard &s : w->shards) free_shard(s);
     if (!w->devices.empty()) (void)hipSetDevice(w->devices[0]);
     if (w->qstream) { (void)hipStreamSynchronize(w->qstream); (void)hipStreamDestroy(w->qstream); }
-    for (DevBuf *b : {&w->h_hits, &w->h_cnt, &w->h_off, &w->h_ids, &w->h_scan, &w->h_in, &w->h_out, &w->h_off_out, &w->h_ids_out}) dev_free(*b);
+    for (DevBuf *b : {&w->h_hits, &w->h_cnt, &w->h_off, &w->h_ids, &w->h_scan, &w->h_in, &w->h_out, &w->h_off_out, &w->h_ids_out, &w->ev_list}) dev_free(*b);
     if (w->q_pin) (void)hipHostFree(w->q_pin);
     delete w;
 }
@@ -1176,6 +1294,7 @@ int edynhip_world_set_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies 
     copy_in(sc.sleeping_disabled, in->sleeping_disabled, n); copy_in(sc.com, in->center_of_mass, 3 * (size_t)n);
     sc.nj = 0; sc.jtype.clear(); sc.jbody.clear(); sc.jpivot.clear(); sc.jaxis.clear(); sc.jparams.clear(); sc.defs.clear(); sc.exclusions.clear();
     w->built = false; w->stepped = false;
+    w->step_count = 0; w->ev_n = 0; w->ev_overflow = false;
     w->stats.num_bodies = n;
     return EDYNHIP_OK;
 }
@@ -1243,6 +1362,8 @@ int edynhip_world_default_should_collide(edynhip_world *w, uint32_t a, uint32_t 
 int edynhip_world_step(edynhip_world *w, uint32_t nsteps) {
     if (!w) return EDYNHIP_ERR_INVALID;
     EH_TRY(ensure_built(w));
+    const bool events = w->events_on();
+    w->ev_n = 0; w->ev_overflow = false;   // the events of THIS call
     for (uint32_t k = 0; k < nsteps; ++k) {
         const bool on_callers_thread = w->pool->run([w](uint32_t r) {
             Shard &s = w->shards[r];
@@ -1253,8 +1374,9 @@ int edynhip_world_step(edynhip_world *w, uint32_t nsteps) {
         });
         if (on_callers_thread) w->paths |= EDYNHIP_PATH_WORLD_SERIAL;
         EH_TRY(shard_error(w));
-        ++w->stats.steps;
+        ++w->stats.steps; ++w->step_count;
         w->stepped = true;
+        if (events) EH_TRY(append_events(w));
         if (w->shards.size() < 2) continue;
         float growth = 0.0f;
         for (Shard &s : w->shards) if (!s.local_ids.empty()) { float g; std::memcpy(&g, s.mon_host, 4); growth = std::max(growth, g); }
@@ -1305,6 +1427,42 @@ int edynhip_world_get_manifolds(edynhip_world *w, edynhip_manifold *out, uint32_
     return EDYNHIP_OK;
 }
 
+int edynhip_world_get_contact_events(edynhip_world *w, edynhip_contact_event *out, uint32_t capacity, uint32_t *n) {
+    static_assert(sizeof(edynhip_contact_event) == sizeof(ContactEvent), "event record layout");
+    if (!w || !n) return EDYNHIP_ERR_INVALID;
+    *n = 0;
+    if (!w->events_on()) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_get_contact_events: create the world with EDYNHIP_FLAG_CONTACT_EVENTS");
+    *n = w->ev_n;
+    if (out) {
+        if (capacity < w->ev_n) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_get_contact_events: capacity too small");
+        if (w->ev_n) {   // the last step's blocks were appended on the shards' streams
+            for (Shard &s : w->shards) if (s.ctx) { W_HIP(w, hipSetDevice(s.device)); W_HIP(w, hipStreamSynchronize(s.ctx->stream)); }
+            W_HIP(w, hipSetDevice(w->devices[0]));
+            W_HIP(w, hipMemcpy(out, w->ev_list.p, (size_t)w->ev_n * sizeof(ContactEvent), hipMemcpyDeviceToHost));
+        }
+    }
+    if (w->ev_overflow) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_get_contact_events: a shard recorded more events than it holds; resynchronise from edynhip_world_get_manifolds and edynhip_world_get_point_ids");
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_get_point_ids(edynhip_world *w, uint64_t *ids, uint32_t capacity_manifolds, uint32_t *n) {
+    if (!w || !n) return EDYNHIP_ERR_INVALID;
+    *n = 0;
+    if (!w->events_on()) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_get_point_ids: create the world with EDYNHIP_FLAG_CONTACT_EVENTS");
+    EH_TRY(ensure_built(w));
+    w->pool->run([w](uint32_t r) { collect_shard(w, r, false, true); });
+    EH_TRY(shard_error(w));
+    std::vector<edynhip_manifold> all;
+    std::vector<uint64_t> all_ids;
+    merge_manifolds(w, all, &all_ids);
+    *n = (uint32_t)all.size();
+    if (ids) {
+        if (capacity_manifolds < all.size()) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_get_point_ids: capacity too small");
+        if (!all_ids.empty()) std::memcpy(ids, all_ids.data(), all_ids.size() * sizeof(uint64_t));
+    }
+    return EDYNHIP_OK;
+}
+
 int edynhip_world_get_stats(edynhip_world *w, edynhip_world_stats *out) {
     if (!w || !out) return EDYNHIP_ERR_INVALID;
     *out = w->stats;
@@ -1337,7 +1495,6 @@ edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard) {
 // caller's arrays and writes its answer in place; any other shard's queries and answers travel device to device.
 namespace {
 
-#define W_HIP(w, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return (w)->fail(EDYNHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
 constexpr uint32_t kWorldChunk = 1u << 20;   // rays per pass (raycast.hip kChunk)
 constexpr unsigned long long kSat32 = 0xFFFFFFFFull;
 

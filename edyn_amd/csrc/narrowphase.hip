@@ -489,8 +489,8 @@ DI void np_merge_lane(const uint32_t m, const Manifolds &mf, const Bodies &b, fl
                     mf.nrm[d] = to4(p.normal, __int_as_float(p.attachment));
                     mf.lnrm[d] = to4(local_normal(p, A, B), restitution);
                     mf.imp[d] = make_float4(0, 0, 0, __uint_as_float(0u));
-                    if (mf.pid) {   // id = (step of creation + 1) << 32 | manifold index << 2 | local slot
-                        const uint64_t id = ((uint64_t)(ev.step + 1u) << 32) | ((uint64_t)m << 2) | (uint64_t)i;
+                    if (mf.pid) {   // id = (step of creation + 1) << 32 | manifold index << 2 | local slot (a shard of a world: | its tag, ctx.hpp)
+                        const uint64_t id = ((uint64_t)(ev.step + 1u) << 32) | (uint64_t)ev.tag | ((uint64_t)m << 2) | (uint64_t)i;
                         mf.pid[slot_at(mf.cap, (uint32_t)n_out, m)] = id;
                         emit_event(ev, EDYNHIP_EVENT_POINT_CREATED, ia, ib, id);
                     }

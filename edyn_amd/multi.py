@@ -25,6 +25,7 @@ class MultiWorld:
         cfg.gravity = (C.c_float * 3)(*[float(x) for x in self.cfg.gravity])
         cfg.flags = ((_capi.FLAG_SLEEPING if self.cfg.sleeping else 0) | (_capi.FLAG_EXCLUSIVE_DEVICE if self.cfg.exclusive_device else 0)
                      | (_capi.FLAG_TIMING_SOLVE if self.cfg.timing_solve else 0)
+                     | (_capi.FLAG_CONTACT_EVENTS if self.cfg.contact_events else 0)
                      | (_capi.FLAG_FUSED_VELOCITY_ROWS if self.cfg.fused_velocity_rows else 0) | (_capi.FLAG_BLOCK_POSITION if self.cfg.block_position else 0))
         dev = np.ascontiguousarray(devices, np.int32)
         st = C.c_int(0)
@@ -107,6 +108,26 @@ class MultiWorld:
         out = np.zeros(max(n.value, 1), MANIFOLD_DTYPE)
         self._check(self._L.edynhip_world_get_manifolds(self._h, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
+
+    # ---- contact events: World.get_contact_events / .get_point_ids on the whole world (init_config(contact_events=True))
+    def get_contact_events(self):
+        """Events of the steps of the last step_simulation() call: structured array (type, step, body[2], point_id) as World returns it -
+        global body indices, the world's step count, ids that survive re-partitions (edynhip_world_get_contact_events)."""
+        n = C.c_uint32(0)
+        self._check(self._L.edynhip_world_get_contact_events(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, _capi.EVENT_DTYPE)
+        if n.value:
+            self._check(self._L.edynhip_world_get_contact_events(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def get_point_ids(self):
+        """[num_manifolds, 4] point ids in get_manifolds() order (0 = no point); edynhip_world_get_point_ids."""
+        m = C.c_uint32(0)
+        self._check(self._L.edynhip_world_get_point_ids(self._h, None, 0, C.byref(m)))
+        out = np.zeros((m.value, 4), np.uint64)
+        if m.value:
+            self._check(self._L.edynhip_world_get_point_ids(self._h, _ptr(out), m.value, C.byref(m)))
+        return out[:m.value]
 
     # ---- queries: World.raycast / World.query_aabb on the whole world, global body indices (edynhip_world_raycast / _query_aabb)
     def raycast(self, p0, p1, ignore=(), brute_force=False):

@@ -650,6 +650,25 @@ int edynhip_world_query_aabb(edynhip_world *w, int category, uint32_t n, const f
                           uint32_t *offsets, uint32_t *ids, uint32_t capacity, uint32_t *total);
 int edynhip_world_query_aabb_device(edynhip_world *w, int category, uint32_t n, const void *boxes_f4, uint32_t flags,
                           void *offsets, void *ids, uint32_t capacity, void *total);
+/* edynhip_get_contact_events / edynhip_get_point_ids on a multi-device world (additive to ABI 15), for a world created with
+ * EDYNHIP_FLAG_CONTACT_EVENTS (without it: EDYNHIP_ERR_UNSUPPORTED). The application sees the event stream and the point identities of
+ * ONE context holding the whole scene; only the VALUES of the point ids differ.
+ *   events: those of all steps of the last edynhip_world_step call (also of the steps before a re-partition inside that call), in no
+ *     particular order within a step; body[] = GLOBAL indices in the order edynhip_world_get_manifolds reports the pair; step = the world's
+ *     steps since edynhip_world_set_bodies. With point_id left out, the multiset of (type, step, body[0], body[1]) is the single
+ *     context's. out == NULL counts; capacity < *n: EDYNHIP_ERR_CAPACITY. A world that is described but not yet stepped has 0 events. If
+ *     one shard recorded more events than its context holds, `n` is capped and EDYNHIP_ERR_CAPACITY is returned (after `out` is filled):
+ *     resynchronise from edynhip_world_get_manifolds + edynhip_world_get_point_ids.
+ *   point ids: ids[4 * i + k] = id of point k of manifold i in edynhip_world_get_manifolds order, 0 where there is no point. An id is
+ *     unique among the living points of the world and stays the same from POINT_CREATED to POINT_DESTROYED, whichever shards the point
+ *     lives on in between: a re-partition - sticky or full, by itself or through edynhip_world_repartition, rebuilt and kept contexts alike -
+ *     emits no event and changes no id. id = (world step of creation + 1) << 32 | shard of creation << 28 | manifold index there << 2 | slot;
+ *     hence at most 16 shards and 2^26 manifolds per shard with this flag (edynhip_world_step: EDYNHIP_ERR_CAPACITY otherwise).
+ * Every shard translates its step's events to global indices on its own device and the blocks are appended, device to device, to one list
+ * on devices[0] (edyn_amd/csrc/world_events.hip); reading the events is one copy from there. A world without the flag runs none of this.
+ * A shard context (edynhip_world_context) stays read-only: its own edynhip_get_contact_events speaks local indices. */
+int edynhip_world_get_contact_events(edynhip_world *w, edynhip_contact_event *out, uint32_t capacity, uint32_t *n);
+int edynhip_world_get_point_ids(edynhip_world *w, uint64_t *ids, uint32_t capacity_manifolds, uint32_t *n);
 /* edynhip_debug_paths of a multi-device world (additive to ABI 15): the OR over every shard context the world has had, plus
  * EDYNHIP_PATH_WORLD_SERIAL when the shards were stepped one after the other on the caller's thread. */
 int edynhip_world_debug_paths(edynhip_world *w, uint64_t *mask);
