@@ -462,10 +462,8 @@ struct edynhip_ctx {
     double *sleep_carried = nullptr;
     long df_solves = 0, dfp_solves = 0;   // dataflow velocity / position solves so far while a trace is asked for (EDYNHIP_DF_TRACE_STEP picks one; solver.hip DfTrace)
     int df_mode = -1;              // dataflow velocity solve: -1 = not probed yet, 0 = unavailable/disabled, 1 = in use
-    uint32_t df_lanes = 0;         // resident waves of the dataflow velocity kernel
+    uint32_t df_resident[5] = {};  // [lanes per manifold: 1, 2, 4] resident waves of that dataflow velocity kernel (0: it cannot be launched)
     uint32_t dfp_waves = 0;        // resident waves of the dataflow position kernel
-    uint32_t df2_waves = 0;        // resident waves of the two-lane dataflow velocity kernel
-    uint32_t df4_waves = 0;        // resident waves of the four-lane dataflow velocity kernel
     bool inplace_step = false;     // broadphase found last step's pair set again and kept the manifold array: islands() has nothing to relabel
     bool points_in_prev = false;   // this step's manifold array holds no copied points yet (see Manifolds::prev_idx)
     bool force_islands = true;     // recompute island labels even if the pair set did not change

@@ -265,44 +265,69 @@ DI void normal_clamp(float &cur, float &dimp, float upper) {
     dimp = (lt || gt) ? nw - cur : dimp;
     cur = nw;
 }
-// One normal row (solve(constraint_row&) + apply_row_impulse) and one friction pair (solve_friction) in either arithmetic.
-template <bool FUSED>
-DI void row_solve_normal(Delta &d, RowReg &r, float upper) {
-    float cur = r.f[2].w;
+// ---- one normal row and one friction pair, written ONCE for every velocity-solve kernel ------------------------------------------------
+// solve(constraint_row&) + apply_row_impulse and solve_friction in either arithmetic (and their warm starts), generic over a LANE LAYOUT L:
+// how many lanes share a manifold and what each of them holds. A layout supplies only
+//   L::Acc, L::Row        what a lane holds of the body deltas and of a row
+//   L::relspeed<FUSED>    the row's relative speed (the same bits in every lane of the manifold)
+//   L::apply<FUSED>       an impulse applied to the lane's share of the deltas
+//   L::eff, L::rhs<FUSED>, L::imp   the row's effective mass, its rhs term (fused: rhs * eff) and its accumulated impulse
+//   L::kLimitFirst        where the reference form multiplies the friction limit (see solve_friction_pair)
+// The layouts: Lanes1 (below: one lane, RowReg / Delta), Lanes2 (two lanes, Row2 / Side) and Lanes4 (four lanes, Row4 / f3) at their kernels.
+// `upper`: the normal row's upper limit - kLarge in the dataflow kernels, the row's own f[4].w (a soft contact's force limit) per colour.
+template <class L, bool WARM, bool FUSED>
+DI void solve_normal_row(typename L::Acc &x, typename L::Row &r, float upper) {
+    if (WARM) { L::template apply<FUSED>(x, r, L::imp(r)); return; }   // warm_start(constraint_row&)
     if (FUSED) {
-        const float applied = fused_normal(cur, fused_delta(row_relspeed<true>(d, r), r.f[0].w, r.f[1].w * r.f[0].w), upper);
-        r.f[2].w = cur;
-        row_apply<true>(d, r, applied);
+        const float applied = fused_normal(L::imp(r), fused_delta(L::template relspeed<true>(x, r), L::eff(r), L::template rhs<true>(r)), upper);
+        L::template apply<true>(x, r, applied);
     } else {
-        const float drel = row_relspeed<false>(d, r);
-        float dimp = (r.f[1].w - drel) * r.f[0].w;
-        normal_clamp(cur, dimp, upper);
-        r.f[2].w = cur;
-        row_apply<false>(d, r, dimp);
+        float dimp = (L::template rhs<false>(r) - L::template relspeed<false>(x, r)) * L::eff(r);
+        normal_clamp(L::imp(r), dimp, upper);
+        L::template apply<false>(x, r, dimp);
     }
 }
-template <bool FUSED>
-DI void row_solve_friction(Delta &d, const RowReg &rn, RowReg &ra, RowReg &rb) {
-    const float max_len = rn.f[3].w * rn.f[2].w;   // mu * current normal impulse
+template <class L, bool WARM, bool FUSED>
+DI void solve_friction_pair(typename L::Acc &x, typename L::Row &ra, typename L::Row &rb, float mu, float normal_imp) {
+    if (WARM) {   // warm_start(constraint_row_friction&)
+        L::template apply<FUSED>(x, ra, L::imp(ra));
+        L::template apply<FUSED>(x, rb, L::imp(rb));
+        return;
+    }
+    const float c0 = L::imp(ra), c1 = L::imp(rb);
     if (FUSED) {
-        const float c0 = ra.f[2].w, c1 = rb.f[2].w;
-        float i0 = c0 + fused_delta(row_relspeed<true>(d, ra), ra.f[0].w, ra.f[1].w * ra.f[0].w);
-        float i1 = c1 + fused_delta(row_relspeed<true>(d, rb), rb.f[0].w, rb.f[1].w * rb.f[0].w);
+        const float max_len = mu * normal_imp;   // mu * current normal impulse
+        float i0 = c0 + fused_delta(L::template relspeed<true>(x, ra), L::eff(ra), L::template rhs<true>(ra));
+        float i1 = c1 + fused_delta(L::template relspeed<true>(x, rb), L::eff(rb), L::template rhs<true>(rb));
         fused_circle(i0, i1, max_len);
-        ra.f[2].w = i0; rb.f[2].w = i1;
-        row_apply<true>(d, ra, i0 - c0);
-        row_apply<true>(d, rb, i1 - c1);
+        L::imp(ra) = i0; L::imp(rb) = i1;
+        L::template apply<true>(x, ra, i0 - c0);
+        L::template apply<true>(x, rb, i1 - c1);
     } else {
-        float di0 = (ra.f[1].w - row_relspeed<false>(d, ra)) * ra.f[0].w;
-        float i0 = ra.f[2].w + di0;
-        float di1 = (rb.f[1].w - row_relspeed<false>(d, rb)) * rb.f[0].w;
-        float i1 = rb.f[2].w + di1;
-        friction_circle(i0, i1, di0, di1, ra.f[2].w, rb.f[2].w, max_len);
-        ra.f[2].w = i0; rb.f[2].w = i1;
-        row_apply<false>(d, ra, di0);
-        row_apply<false>(d, rb, di1);
+        // L::kLimitFirst: whether the limit is formed before or after the two relative speeds. The value is the same; the compiler's
+        // instruction schedule follows the place, and each layout keeps the place its kernels were measured with. It has no other
+        // meaning: drop it (one place for all layouts) the next time these kernels are measured again anyway.
+        float max_len = L::kLimitFirst ? mu * normal_imp : 0.0f;
+        float di0 = (L::template rhs<false>(ra) - L::template relspeed<false>(x, ra)) * L::eff(ra);
+        float i0 = c0 + di0;
+        float di1 = (L::template rhs<false>(rb) - L::template relspeed<false>(x, rb)) * L::eff(rb);
+        float i1 = c1 + di1;
+        if (!L::kLimitFirst) max_len = mu * normal_imp;
+        friction_circle(i0, i1, di0, di1, c0, c1, max_len);
+        L::imp(ra) = i0; L::imp(rb) = i1;
+        L::template apply<false>(x, ra, di0);
+        L::template apply<false>(x, rb, di1);
     }
 }
+struct Lanes1 {   // one lane per manifold: both bodies' deltas and the whole rows (rhs * eff is multiplied at use)
+    typedef Delta Acc; typedef RowReg Row;
+    static constexpr bool kLimitFirst = true;
+    template <bool FUSED> static DI float relspeed(const Delta &d, const RowReg &r) { return row_relspeed<FUSED>(d, r); }
+    template <bool FUSED> static DI void apply(Delta &d, const RowReg &r, float imp) { row_apply<FUSED>(d, r, imp); }
+    static DI float eff(const RowReg &r) { return r.f[0].w; }
+    template <bool FUSED> static DI float rhs(const RowReg &r) { return FUSED ? r.f[1].w * r.f[0].w : r.f[1].w; }
+    static DI float &imp(RowReg &r) { return r.f[2].w; }
+};
 // NP (points of the manifold) is a template parameter: lanes are grouped by point count inside a colour, so a wave
 // runs one instantiation, every loop is fully unrolled without predication and the compiler can issue all
 // 15*NP row loads plus the body loads back to back before the first use (one memory round trip after the indices).
@@ -326,18 +351,12 @@ DI void rows_solve(Delta &d, RowReg (&R)[NP][kRowsPerPoint], uint32_t np) {
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         if ((uint32_t)k >= np) continue;
-        RowReg &r = R[k][0];
-        if (WARM) row_apply<FUSED>(d, r, r.f[2].w);
-        else row_solve_normal<FUSED>(d, r, r.f[4].w);   // upper = large_scalar, or a soft contact's force limit
+        solve_normal_row<Lanes1, WARM, FUSED>(d, R[k][0], R[k][0].f[4].w);   // upper = large_scalar, or a soft contact's force limit
     }
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         if ((uint32_t)k >= np) continue;
-        RowReg &ra = R[k][1], &rb = R[k][2];
-        if (WARM) {   // warm_start(constraint_row_friction&)
-            row_apply<FUSED>(d, ra, ra.f[2].w);
-            row_apply<FUSED>(d, rb, rb.f[2].w);
-        } else row_solve_friction<FUSED>(d, R[k][0], ra, rb);
+        solve_friction_pair<Lanes1, WARM, FUSED>(d, R[k][1], R[k][2], R[k][0].f[3].w, R[k][0].f[2].w);
     }
 }
 template <int NP>
@@ -360,16 +379,8 @@ DI void rows_solve_normals(Delta &d, RowReg (&Rn)[NP], uint32_t np) {
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         if ((uint32_t)k >= np) continue;
-        if (WARM) row_apply<FUSED>(d, Rn[k], Rn[k].f[2].w);
-        else row_solve_normal<FUSED>(d, Rn[k], kLarge);
+        solve_normal_row<Lanes1, WARM, FUSED>(d, Rn[k], kLarge);
     }
-}
-template <bool WARM, bool FUSED>
-DI void rows_solve_friction(Delta &d, const RowReg &rn, RowReg &ra, RowReg &rb) {
-    if (WARM) {   // warm_start(constraint_row_friction&)
-        row_apply<FUSED>(d, ra, ra.f[2].w);
-        row_apply<FUSED>(d, rb, rb.f[2].w);
-    } else row_solve_friction<FUSED>(d, rn, ra, rb);
 }
 // contact_extras rows of one manifold after its normal and friction rows: the rolling pairs of all points, then the
 // spinning rows (island_solver.cpp:76-111 keeps the row kinds in this order). Rolling is solve_friction with the roll
@@ -580,6 +591,14 @@ DI void df_publish(float4 *slot, f3 dv, f3 dw, uint32_t tag) {   // slot = &dslo
                  "global_store_dwordx4 %0, %2, off offset:1024 sc1" : : "v"(slot), "v"(v), "v"(w) : "memory");
 }
 constexpr uint32_t kDfSpinLimit = 1u << 22;   // ~seconds; a hand-off normally arrives within microseconds
+// (Measured and dropped: the wait loop below - ballot, lowest pending colour, watchdog, trace stamps - and the (sweep, round) task loop are
+//  spelled out in each of the four dataflow kernels. Written once (a struct holding the round's protocol, called from each task's loop,
+//  and one task walker; as lambdas the position kernel got 176 bytes of scratch), outputs stayed byte-equal and no kernel gained scratch
+//  or lost occupancy, but the compiler's code differed in all eight instantiations, and alternating runs against the parent on one box
+//  lost 0.6-1.7 % where the parent's own spread over three runs is 0.1-0.6 %: mixed32k 718.7 against 723.1 steps/s, EDYNHIP_DF_LANES=1
+//  741.9 against 751.5; the default pile, four lanes and chains16k stayed level. With the one-lane kernel back in the parent's form and the
+//  two-lane kernel back on the parent's task loop, the rest still shared: mixed32k 716.3 against 722.9, fused arithmetic 894.5 against
+//  909.7. So the four copies stay, and a fix in one of them still has to be made in all four.)
 template <bool WARM, int NP, bool FUSED>
 DI void df_task(const DfArgs &a, uint32_t p, bool valid, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *trace_slot) {
     // Rows fetched before the wait: every normal row and the friction rows of the first two points. The friction rows
@@ -628,7 +647,7 @@ DI void df_task(const DfArgs &a, uint32_t p, bool valid, uint32_t np, uint32_t c
                 rows_solve_normals<WARM, NP, FUSED>(d, Rn, np);
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
-                    if ((uint32_t)k < np) rows_solve_friction<WARM, FUSED>(d, Rn[k], Rf[k][0], Rf[k][1]);
+                    if ((uint32_t)k < np) solve_friction_pair<Lanes1, WARM, FUSED>(d, Rf[k][0], Rf[k][1], Rn[k].f[3].w, Rn[k].f[2].w);
                 // hand the deltas over first (the next manifolds are waiting for them), then store the impulses
                 if (d.imA != 0) df_publish(a.dslot + dslot_at(nA & kSlotMask, 0), d.dvA, d.dwA, sweep + 1);
                 if (d.imB != 0) df_publish(a.dslot + dslot_at(nB & kSlotMask, 0), d.dvB, d.dwB, sweep + 1);
@@ -1525,50 +1544,15 @@ DI void df2_apply(Side &x, const Row2 &r, float imp) {
     if (FUSED) { x.dv = fma3(r.ijl, imp, x.dv); x.dw = fma3(r.ija, imp, x.dw); }
     else { x.dv += r.ijl * imp; x.dw += r.ija * imp; }
 }
-template <bool WARM, bool FUSED>
-DI void df2_point(Side &x, Row2 (&R)[kRowsPerPoint], float mu) {
-    Row2 &rn = R[0];
-    if (WARM) {   // warm_start: the normal row, then the friction pair
-        df2_apply<FUSED>(x, rn, rn.imp);
-        return;
-    }
-    if (FUSED) {
-        const float applied = fused_normal(rn.imp, fused_delta(df2_relspeed<true>(x, rn), rn.eff, rn.rhs), kLarge);
-        df2_apply<true>(x, rn, applied);
-    } else {
-        float dimp = (rn.rhs - df2_relspeed<false>(x, rn)) * rn.eff;
-        normal_clamp(rn.imp, dimp, kLarge);
-        df2_apply<false>(x, rn, dimp);
-    }
-    (void)mu;
-}
-template <bool WARM, bool FUSED>
-DI void df2_friction(Side &x, Row2 (&R)[kRowsPerPoint], float mu) {
-    Row2 &ra = R[1], &rb = R[2];
-    if (WARM) {   // warm_start(constraint_row_friction&)
-        df2_apply<FUSED>(x, ra, ra.imp);
-        df2_apply<FUSED>(x, rb, rb.imp);
-        return;
-    }
-    const float c0 = ra.imp, c1 = rb.imp;
-    if (FUSED) {
-        float i0 = c0 + fused_delta(df2_relspeed<true>(x, ra), ra.eff, ra.rhs);
-        float i1 = c1 + fused_delta(df2_relspeed<true>(x, rb), rb.eff, rb.rhs);
-        fused_circle(i0, i1, mu * R[0].imp);   // mu * current normal impulse
-        ra.imp = i0; rb.imp = i1;
-        df2_apply<true>(x, ra, i0 - c0);
-        df2_apply<true>(x, rb, i1 - c1);
-    } else {
-        float di0 = (ra.rhs - df2_relspeed<false>(x, ra)) * ra.eff;
-        float i0 = c0 + di0;
-        float di1 = (rb.rhs - df2_relspeed<false>(x, rb)) * rb.eff;
-        float i1 = c1 + di1;
-        friction_circle(i0, i1, di0, di1, c0, c1, mu * R[0].imp);   // mu * current normal impulse
-        ra.imp = i0; rb.imp = i1;
-        df2_apply<false>(x, ra, di0);
-        df2_apply<false>(x, rb, di1);
-    }
-}
+struct Lanes2 {   // two lanes per manifold: each holds its own body's deltas and its side's pieces of the rows (Row2::rhs is rhs * eff in the fused form)
+    typedef Side Acc; typedef Row2 Row;
+    static constexpr bool kLimitFirst = false;
+    template <bool FUSED> static DI float relspeed(const Side &x, const Row2 &r) { return df2_relspeed<FUSED>(x, r); }
+    template <bool FUSED> static DI void apply(Side &x, const Row2 &r, float imp) { df2_apply<FUSED>(x, r, imp); }
+    static DI float eff(const Row2 &r) { return r.eff; }
+    template <bool FUSED> static DI float rhs(const Row2 &r) { return r.rhs; }
+    static DI float &imp(Row2 &r) { return r.imp; }
+};
 // EXACT: every live lane of the wave has exactly NP points (the common case: lanes are grouped by point count), so the
 // rows need no per-lane point-count predicate.
 template <bool WARM, int NP, bool EXACT, bool FUSED>
@@ -1626,10 +1610,10 @@ DI void df2_task(const DfArgs &a, uint32_t p, bool valid, bool sideB, uint32_t n
             if (mine_now) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
-                    if (EXACT || (uint32_t)k < np) df2_point<WARM, FUSED>(x, R[k], mu[k]);
+                    if (EXACT || (uint32_t)k < np) solve_normal_row<Lanes2, WARM, FUSED>(x, R[k][0], kLarge);
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
-                    if (EXACT || (uint32_t)k < np) df2_friction<WARM, FUSED>(x, R[k], mu[k]);
+                    if (EXACT || (uint32_t)k < np) solve_friction_pair<Lanes2, WARM, FUSED>(x, R[k][1], R[k][2], mu[k], R[k][0].imp);
                 // hand the deltas over first (the next manifold of this body is waiting for them), then store the impulses
                 if (im != 0) df_publish(a.dslot + dslot_at(nx & kSlotMask, 0), x.dv, x.dw, sweep + 1);
                 if (!WARM && sideB) {
@@ -1743,45 +1727,15 @@ DI float df4_relspeed(const f3 &x, const Row4 &r) {   // roles 0..3 = A linear, 
 }
 template <bool FUSED>
 DI void df4_apply(f3 &x, const Row4 &r, float imp) { if (FUSED) x = fma3(r.ij, imp, x); else x += r.ij * imp; }
-template <bool WARM, bool FUSED>
-DI void df4_normal(f3 &x, Row4 &rn) {   // Row4::rhs: the row's rhs (reference arithmetic) or rhs * eff (fused)
-    if (WARM) { df4_apply<FUSED>(x, rn, rn.imp); return; }
-    if (FUSED) {
-        const float applied = fused_normal(rn.imp, fused_delta(df4_relspeed<true>(x, rn), rn.eff, rn.rhs), kLarge);
-        df4_apply<true>(x, rn, applied);
-    } else {
-        float dimp = (rn.rhs - df4_relspeed<false>(x, rn)) * rn.eff;
-        normal_clamp(rn.imp, dimp, kLarge);
-        df4_apply<false>(x, rn, dimp);
-    }
-}
-template <bool WARM, bool FUSED>
-DI void df4_friction(f3 &x, Row4 (&R)[kRowsPerPoint], float mu) {
-    Row4 &ra = R[1], &rb = R[2];
-    if (WARM) {   // warm_start(constraint_row_friction&)
-        df4_apply<FUSED>(x, ra, ra.imp);
-        df4_apply<FUSED>(x, rb, rb.imp);
-        return;
-    }
-    const float c0 = ra.imp, c1 = rb.imp;
-    if (FUSED) {
-        float i0 = c0 + fused_delta(df4_relspeed<true>(x, ra), ra.eff, ra.rhs);
-        float i1 = c1 + fused_delta(df4_relspeed<true>(x, rb), rb.eff, rb.rhs);
-        fused_circle(i0, i1, mu * R[0].imp);   // mu * current normal impulse
-        ra.imp = i0; rb.imp = i1;
-        df4_apply<true>(x, ra, i0 - c0);
-        df4_apply<true>(x, rb, i1 - c1);
-    } else {
-        float di0 = (ra.rhs - df4_relspeed<false>(x, ra)) * ra.eff;
-        float i0 = c0 + di0;
-        float di1 = (rb.rhs - df4_relspeed<false>(x, rb)) * rb.eff;
-        float i1 = c1 + di1;
-        friction_circle(i0, i1, di0, di1, c0, c1, mu * R[0].imp);
-        ra.imp = i0; rb.imp = i1;
-        df4_apply<false>(x, ra, di0);
-        df4_apply<false>(x, rb, di1);
-    }
-}
+struct Lanes4 {   // four lanes per manifold: each holds one 3-vector of the deltas and its piece of the rows (Row4::rhs is rhs * eff in the fused form)
+    typedef f3 Acc; typedef Row4 Row;
+    static constexpr bool kLimitFirst = false;
+    template <bool FUSED> static DI float relspeed(const f3 &x, const Row4 &r) { return df4_relspeed<FUSED>(x, r); }
+    template <bool FUSED> static DI void apply(f3 &x, const Row4 &r, float imp) { df4_apply<FUSED>(x, r, imp); }
+    static DI float eff(const Row4 &r) { return r.eff; }
+    template <bool FUSED> static DI float rhs(const Row4 &r) { return r.rhs; }
+    static DI float &imp(Row4 &r) { return r.imp; }
+};
 template <bool WARM, int NP, bool EXACT, bool FUSED>
 DI void df4_task(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *trace_slot) {
     Row4 R[NP][kRowsPerPoint];
@@ -1836,10 +1790,10 @@ DI void df4_task(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_
             if (mine_now) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
-                    if (EXACT || (uint32_t)k < np) df4_normal<WARM, FUSED>(x, R[k][0]);
+                    if (EXACT || (uint32_t)k < np) solve_normal_row<Lanes4, WARM, FUSED>(x, R[k][0], kLarge);
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
-                    if (EXACT || (uint32_t)k < np) df4_friction<WARM, FUSED>(x, R[k], mu[k]);
+                    if (EXACT || (uint32_t)k < np) solve_friction_pair<Lanes4, WARM, FUSED>(x, R[k][1], R[k][2], mu[k], R[k][0].imp);
                 // hand the deltas over first (the next manifold of this body is waiting for them), then store the impulses
                 if (im != 0) df4_publish(a.dslot + dslot_at(nx & kSlotMask, ang ? 1u : 0u), x, sweep + 1);
                 if (!WARM && role == 3u) {
@@ -2709,22 +2663,17 @@ static const void *df_position_fn(bool block) { return block ? (const void *)k_p
 // at 1 when the dataflow schedules can be used (EDYNHIP_DATAFLOW=0 or a device without cooperative launches: 0).
 static void probe_dataflow(edynhip_ctx *c, bool fused_rows, bool block_pos) {
     c->df_mode = 0;
-    int per_cu = 0, ncu = 0, coop = 0;
+    int ncu = 0, coop = 0;
     if (c->knobs.dataflow &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, df_velocity_fn(1u, fused_rows), kDfBlock, 0) == hipSuccess &&
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess &&
-        hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && per_cu > 0 && ncu > 0 && coop) {
-        c->df_lanes = (uint32_t)per_cu * (uint32_t)ncu;   // resident waves (one per workgroup)
-        int per_cu2 = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, df_velocity_fn(2u, fused_rows), 64, 0) == hipSuccess && per_cu2 > 0)
-            c->df2_waves = (uint32_t)per_cu2 * (uint32_t)ncu;
-        int per_cu4 = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, df_velocity_fn(4u, fused_rows), 64, 0) == hipSuccess && per_cu4 > 0)
-            c->df4_waves = (uint32_t)per_cu4 * (uint32_t)ncu;
-        int per_cu_p = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_p, df_position_fn(block_pos), 64, 0) == hipSuccess && per_cu_p > 0)
-            c->dfp_waves = (uint32_t)per_cu_p * (uint32_t)ncu;
-        c->df_mode = 1;
+        hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && ncu > 0 && coop) {
+        auto resident = [&](const void *fn) {   // one wave per workgroup
+            int per_cu = 0;
+            return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kDfBlock, 0) == hipSuccess && per_cu > 0 ? (uint32_t)per_cu * (uint32_t)ncu : 0u;
+        };
+        for (uint32_t lanes : {1u, 2u, 4u}) c->df_resident[lanes] = resident(df_velocity_fn(lanes, fused_rows));
+        c->dfp_waves = resident(df_position_fn(block_pos));
+        if (c->df_resident[1] > 0) c->df_mode = 1;   // (the one-lane kernel is what the others fall back to)
     }
     (void)hipGetLastError();
 }
@@ -2810,17 +2759,17 @@ static SolvePlan plan_solve(const edynhip_ctx *c) {
         // or 1 (k_contact_solve_df: least row traffic, for bandwidth-bound scenes - many islands, millions of points). EDYNHIP_DF_LANES forces one.
         // (the multi-lane forms read J_lin on two lanes: ~20 % more row traffic, which only matters once the sweep is
         // bandwidth-bound - then the one-lane kernel is the better one)
-        const bool latency_bound = c->df2_waves > 0 && na <= 16u * 32u * c->df2_waves;
+        const bool latency_bound = c->df_resident[2] > 0 && na <= 16u * 32u * c->df_resident[2];
         // Four lanes were measured on the settled headline pile (r03): 541 instead of 633 instructions between "inputs arrived" and
         // "published" (1.50 vs 1.66 us per wave-task), but 16 manifolds per wave need two waves per SIMD for the same ~4.5 tasks per
         // wave and sweep, and the two contend for the issue slots exactly while the critical chain runs: 0.60 vs 0.564 ms per solve.
         // Two lanes stay the default; EDYNHIP_DF_LANES=4 selects the four-lane kernel (bit-identical).
         uint32_t lanes = latency_bound ? 2u : 1u;
         if (kn.df_lanes == 1 || kn.df_lanes == 2 || kn.df_lanes == 4) lanes = (uint32_t)kn.df_lanes;
-        if (lanes == 4u && c->df4_waves == 0) lanes = 2u;
-        if (lanes == 2u && c->df2_waves == 0) lanes = 1u;
+        if (lanes == 4u && c->df_resident[4] == 0) lanes = 2u;
+        if (lanes == 2u && c->df_resident[2] == 0) lanes = 1u;
         const uint32_t per_wave = 64u / lanes;
-        const uint32_t resident = lanes == 4u ? c->df4_waves : lanes == 2u ? c->df2_waves : c->df_lanes;
+        const uint32_t resident = c->df_resident[lanes];
         const uint32_t want_waves = kn.df_waves ? (uint32_t)kn.df_waves : std::max(lanes == 4u ? 2048u : lanes == 2u ? 1024u : 512u, blocks(na, per_wave * 9));
         p.lanes = lanes;
         p.vel_grid = std::min(blocks(na, per_wave), std::min(resident, want_waves));

@@ -15,7 +15,7 @@ Everything is bit-exact: there is no tolerance in this file.
 
 When is a knob live (DESIGN.md section 4 has the same list):
   EDYNHIP_DF_WAVES / DF_LANES    always on a contact-only scene; more than one round per wave needs na > waves * 64 / lanes
-  EDYNHIP_DF_LANES=4             needs the four-lane kernel resident (df4_waves > 0), else it falls back to 2: the lanes bit tells
+  EDYNHIP_DF_LANES=4             needs the four-lane kernel resident (df_resident[4] > 0), else it falls back to 2: the lanes bit tells
   EDYNHIP_DFP_WAVES              always on a contact-only scene; more than one round needs na > waves * 32
   EDYNHIP_DF_NAP                 a kernel argument of the two-lane velocity kernel, whenever that kernel is launched (bit: a value other than 1)
   EDYNHIP_DF_XCD                 only with a grid that is a multiple of 8 and at least 64 workgroups: na >= 2017 and DF_WAVES=64 / DFP_WAVES=64
