@@ -57,6 +57,10 @@ class WorldStats(C.Structure):   # edynhip_world_stats
     _fields_ = [(n, C.c_uint32) for n in ("num_shards", "num_bodies", "steps", "approach_checks", "repartitions")] + [("bodies_per_shard", C.c_uint32 * 16), ("rebalances", C.c_uint32)]
 
 
+class WorldEditStats(C.Structure):   # edynhip_world_edit_stats
+    _fields_ = [(n, C.c_uint32) for n in ("edits", "in_place", "shard_rebuilds", "repartitions_by_edit", "approach_checks_by_edit")]
+
+
 SCHEDULE_NAMES = {0: "none", 1: "k_contact_solve_df2 (dataflow, one launch per step, two lanes per manifold)",
                   2: "k_contact_solve_df (dataflow, one launch per step, one lane per manifold)",
                   3: "k_island_velocity (island-fused: one wave per island)",
@@ -131,7 +135,11 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats",
            "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device",
            "edynhip_world_get_contact_events", "edynhip_world_get_point_ids",
-           "edynhip_debug_paths", "edynhip_world_debug_paths"]
+           "edynhip_debug_paths", "edynhip_world_debug_paths",
+           # edits of a running multi-device world
+           "edynhip_world_add_bodies", "edynhip_world_remove_bodies", "edynhip_world_add_joints", "edynhip_world_remove_joints",
+           "edynhip_world_edit_joint", "edynhip_world_edit_exclusion", "edynhip_world_set_state", "edynhip_world_get_params",
+           "edynhip_world_set_params", "edynhip_world_get_edit_stats", "edynhip_world_get_asleep"]
 
 _lib = None
 
@@ -242,6 +250,17 @@ def lib():
                                                       C.c_void_p]
         L.edynhip_world_get_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_world_get_point_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.edynhip_world_add_bodies.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Bodies), C.POINTER(C.c_uint32)]
+        L.edynhip_world_remove_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_world_add_joints.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Joints), C.POINTER(C.c_uint32)]
+        L.edynhip_world_remove_joints.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_world_edit_joint.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.edynhip_world_edit_exclusion.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
+        L.edynhip_world_set_state.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        L.edynhip_world_get_params.argtypes = [C.c_void_p, C.POINTER(Params)]
+        L.edynhip_world_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
+        L.edynhip_world_get_edit_stats.argtypes = [C.c_void_p, C.POINTER(WorldEditStats)]
+        L.edynhip_world_get_asleep.argtypes = [C.c_void_p, C.c_void_p]
         L.edynhip_partition_islands.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_island_boxes_overlap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_get_island_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]

@@ -231,6 +231,7 @@ struct HostScene {   // deep copy of what the caller described, in global indice
     std::vector<int32_t> jtype;
     std::vector<uint32_t> jbody;
     std::vector<float> jpivot, jaxis, jparams;
+    std::vector<uint8_t> jalive;          // per joint: 0 once removed (edits of a running world: the index stays reserved)
     struct Def { uint32_t joint; bool generic; std::vector<float> fa, fb, p; };
     std::vector<Def> defs;
     std::vector<std::array<uint32_t, 2>> exclusions;
@@ -260,6 +261,7 @@ struct Shard {
     // monitor scratch on the device: [0] growth bits, [1] island count | per label 3 lo + 3 hi ordered bits | out labels | out boxes | amin0 | amax0
     uint32_t *mon_dev = nullptr, *mon_host = nullptr;
     uint32_t cap = 0, joint_cap = 0, meshes_created = 0;
+    uint32_t want_bodies = 0, want_joints = 0;   // head-room an edit asks of the next build_shard beyond what the scene holds now
     int rc = EDYNHIP_OK;
     std::string err;
     uint64_t paths_gone = 0;              // edynhip_debug_paths of the contexts this shard had before (free_shard)
@@ -371,6 +373,14 @@ struct edynhip_world {
     uint32_t ev_n = 0, step_count = 0;
     bool ev_overflow = false;
     bool events_on() const { return (cfg.flags & EDYNHIP_FLAG_CONTACT_EVENTS) != 0; }
+    // edits of a running world (edynhip_world_add_bodies ...): tombstones per global body, the settings last given to
+    // edynhip_world_set_params (applied to every context built afterwards), and which path the edits took
+    std::vector<uint8_t> removed;
+    std::vector<uint32_t> pending_tombs;           // removed since the last step: still described as they were (scene_tombstones)
+    bool params_set = false;
+    edynhip_params params{};
+    edynhip_world_edit_stats edit_stats{};
+    bool is_removed(uint32_t g) const { return g < removed.size() && removed[g] != 0; }
 };
 
 namespace {
@@ -413,6 +423,42 @@ std::vector<T> take(const std::vector<T> &src, const std::vector<uint32_t> &ids,
     for (size_t k = 0; k < ids.size(); ++k) std::memcpy(&out[k * width], &src[(size_t)ids[k] * width], width * sizeof(T));
     return out;
 }
+
+template <typename T> std::vector<T> rows_of(const T *src, const std::vector<uint32_t> &rows, size_t width) {
+    std::vector<T> out;
+    if (!src) return out;
+    out.resize(rows.size() * width);
+    for (size_t k = 0; k < rows.size(); ++k) std::memcpy(&out[k * width], src + (size_t)rows[k] * width, width * sizeof(T));
+    return out;
+}
+template <typename T> const T *data_or_null(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+
+// The rows `rows` of a body set as a body set of their own (what a shard's context is given): every array edynhip_bodies has, in one
+// place - build_shard slices the scene with it, edynhip_world_add_bodies the caller's new bodies.
+struct BodyRows {
+    std::vector<int32_t> kind, shape_type;
+    std::vector<float> pos, orn, linvel, angvel, mass, inertia, shape_param, friction, restitution, gravity, com;
+    std::vector<uint8_t> has_inertia, sleeping_disabled;
+    std::vector<uint64_t> group, mask;
+    BodyRows(const edynhip_bodies &in, const std::vector<uint32_t> &rows) {
+        const bool own_inertia = in.inertia && in.has_inertia;
+        kind = rows_of(in.kind, rows, 1); shape_type = rows_of(in.shape_type, rows, 1);
+        pos = rows_of(in.pos, rows, 3); orn = rows_of(in.orn, rows, 4); linvel = rows_of(in.linvel, rows, 3); angvel = rows_of(in.angvel, rows, 3);
+        mass = rows_of(in.mass, rows, 1); shape_param = rows_of(in.shape_param, rows, 4); friction = rows_of(in.friction, rows, 1); restitution = rows_of(in.restitution, rows, 1);
+        inertia = rows_of(own_inertia ? in.inertia : nullptr, rows, 9); has_inertia = rows_of(own_inertia ? in.has_inertia : nullptr, rows, 1);
+        group = rows_of(in.group, rows, 1); mask = rows_of(in.mask, rows, 1); gravity = rows_of(in.gravity, rows, 3);
+        sleeping_disabled = rows_of(in.sleeping_disabled, rows, 1); com = rows_of(in.center_of_mass, rows, 3);
+    }
+    edynhip_bodies view() const {
+        edynhip_bodies b{};
+        b.kind = kind.data(); b.pos = pos.data(); b.orn = orn.data(); b.linvel = linvel.data(); b.angvel = angvel.data(); b.mass = mass.data();
+        b.inertia = data_or_null(inertia); b.has_inertia = data_or_null(has_inertia);
+        b.shape_type = shape_type.data(); b.shape_param = shape_param.data(); b.friction = friction.data(); b.restitution = restitution.data();
+        b.group = data_or_null(group); b.mask = data_or_null(mask); b.gravity = data_or_null(gravity);
+        b.sleeping_disabled = data_or_null(sleeping_disabled); b.center_of_mass = data_or_null(com);
+        return b;
+    }
+};
 
 // layout of the monitor scratch (Shard::mon_dev, edynhip_get_island_boxes), in 32-bit words, for `cap` bodies:
 //   [0] growth bits  [1] island count | per label 3 lo + 3 hi ordered bits | out labels | out boxes (6 floats) | pad | amin0 | amax0 (float4 each)
@@ -484,6 +530,7 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     // joints whose bodies are here and of which this shard owns one (a joint to a replicated anchor lives on one shard)
     s.local_joints.clear();
     for (uint32_t g = 0; g < sc.nj; ++g) {
+        if (!sc.jalive[g]) continue;   // removed on the running world: its index stays reserved, no context holds it any more
         const uint32_t a = sc.jbody[2 * g], b = sc.jbody[2 * g + 1];
         // a joint is an island edge: a partition that puts its two dynamic bodies on different shards is wrong - never drop it silently
         if (w->rank_of[a] >= 0 && w->rank_of[b] >= 0 && w->rank_of[a] != w->rank_of[b]) {
@@ -499,12 +546,15 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     // world on an existing context (manifolds, joints, exclusions, sleep state, clocks - everything but the meshes, which are the scene's
     // and stay), and a context's ~100 device allocations - over a gigabyte for a 32k-body shard - are neither freed nor made again
     // (round 6: the frees and allocations were ~0.1 s of every re-partition). A context that is too small is replaced with head-room.
-    const bool reuse = s.ctx != nullptr && nl <= s.cap && (uint32_t)s.local_joints.size() <= s.joint_cap && (uint32_t)sc.meshes.size() == s.meshes_created;
+    // (an edit that did not fit asks for room beyond the scene as it stands: want_bodies / want_joints)
+    const uint32_t need_b = nl + s.want_bodies, need_j = (uint32_t)s.local_joints.size() + s.want_joints;
+    s.want_bodies = s.want_joints = 0;
+    const bool reuse = s.ctx != nullptr && need_b <= s.cap && need_j <= s.joint_cap && (uint32_t)sc.meshes.size() == s.meshes_created;
     if (!reuse) {
         free_shard(s);
         trace.mark("free the old context");
-        cfg.max_bodies = std::max<uint32_t>(nl + nl / 4 + 64, 64);
-        cfg.max_joints = std::max<uint32_t>((uint32_t)s.local_joints.size() + (uint32_t)s.local_joints.size() / 4 + 16, 16);
+        cfg.max_bodies = std::max<uint32_t>(need_b + need_b / 4 + 64, 64);
+        cfg.max_joints = std::max<uint32_t>(need_j + need_j / 4 + 16, 16);
         int status = 0;
         s.ctx = edynhip_create(&cfg, &status);
         if (!s.ctx) { s.rc = status; s.err = edynhip_last_error(nullptr); return; }
@@ -519,6 +569,7 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     } else {
         SH_TRY(s, edynhip_synchronize(s.ctx));
     }
+    if (w->params_set) SH_TRY(s, edynhip_set_params(s.ctx, &w->params));   // (gravity equals cfg.gravity: only the settings a config does not carry)
     if (w->events_on()) {
         // World point ids: (world step of creation + 1) << 32 | shard << 28 | manifold index << 2 | slot. The context counts the world's steps
         // (its own step_index restarts with edynhip_set_bodies below) and tags the ids it issues, so events and ids are in world terms natively.
@@ -533,23 +584,18 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     }
     // bodies: the scene's definitions with the CURRENT state
     const std::vector<float> &P = from_state ? w->pos : sc.pos, &Q = from_state ? w->orn : sc.orn, &V = from_state ? w->linvel : sc.linvel, &W = from_state ? w->angvel : sc.angvel;
-    auto kind = take(sc.kind, s.local_ids, 1), shape_type = take(sc.shape_type, s.local_ids, 1);
-    auto pos = take(P, s.local_ids, 3), orn = take(Q, s.local_ids, 4), lv = take(V, s.local_ids, 3), av = take(W, s.local_ids, 3);
-    auto mass = take(sc.mass, s.local_ids, 1), inertia = take(sc.inertia, s.local_ids, 9), sp = take(sc.shape_param, s.local_ids, 4);
-    auto fr = take(sc.friction, s.local_ids, 1), re = take(sc.restitution, s.local_ids, 1), gr = take(sc.gravity, s.local_ids, 3), com = take(sc.com, s.local_ids, 3);
-    auto hi = take(sc.has_inertia, s.local_ids, 1), sd = take(sc.sleeping_disabled, s.local_ids, 1);
-    auto group = take(sc.group, s.local_ids, 1), mask = take(sc.mask, s.local_ids, 1);
-    edynhip_bodies b{};
-    b.kind = kind.data(); b.pos = pos.data(); b.orn = orn.data(); b.linvel = lv.data(); b.angvel = av.data(); b.mass = mass.data();
-    b.inertia = inertia.empty() ? nullptr : inertia.data(); b.has_inertia = hi.empty() ? nullptr : hi.data();
-    b.shape_type = shape_type.data(); b.shape_param = sp.data(); b.friction = fr.data(); b.restitution = re.data();
-    b.group = group.empty() ? nullptr : group.data(); b.mask = mask.empty() ? nullptr : mask.data();
-    b.gravity = gr.empty() ? nullptr : gr.data(); b.sleeping_disabled = sd.empty() ? nullptr : sd.data();
-    b.center_of_mass = com.empty() ? nullptr : com.data();
+    edynhip_bodies whole{};
+    whole.kind = sc.kind.data(); whole.pos = P.data(); whole.orn = Q.data(); whole.linvel = V.data(); whole.angvel = W.data(); whole.mass = sc.mass.data();
+    whole.inertia = data_or_null(sc.inertia); whole.has_inertia = data_or_null(sc.has_inertia);
+    whole.shape_type = sc.shape_type.data(); whole.shape_param = sc.shape_param.data(); whole.friction = sc.friction.data(); whole.restitution = sc.restitution.data();
+    whole.group = data_or_null(sc.group); whole.mask = data_or_null(sc.mask); whole.gravity = data_or_null(sc.gravity);
+    whole.sleeping_disabled = data_or_null(sc.sleeping_disabled); whole.center_of_mass = data_or_null(sc.com);
+    const BodyRows mine(whole, s.local_ids);
+    const edynhip_bodies b = mine.view();
     SH_TRY(s, edynhip_set_bodies(s.ctx, nl, &b));
     trace.mark("take + edynhip_set_bodies");
-    if (from_state && !com.empty()) {   // set_bodies read `pos` as the origin of bodies with an offset: put the centre-of-mass state back ...
-        SH_TRY(s, edynhip_set_state(s.ctx, pos.data(), orn.data(), lv.data(), av.data()));
+    if (from_state && !mine.com.empty()) {   // set_bodies read `pos` as the origin of bodies with an offset: put the centre-of-mass state back ...
+        SH_TRY(s, edynhip_set_state(s.ctx, mine.pos.data(), mine.orn.data(), mine.linvel.data(), mine.angvel.data()));
         // ... and with it what set_bodies derived from the misread position: origins, AABBs (displaced by R com otherwise - the first
         // broadphase / narrowphase after a re-partition would place those shapes wrong) and world inertias. Before the sleep tags below:
         // the derivation skips sleeping bodies
@@ -624,6 +670,11 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
             }
             SH_TRY(s, edynhip_set_sleep_timers(s.ctx, lab.data(), since.data(), carry.clock));
         }
+    }
+    {   // bodies removed since the last step went up as they were described, with their manifolds: now the removal itself, as the old context took it
+        std::vector<uint32_t> gone;
+        for (uint32_t g : w->pending_tombs) if (s.to_local[g] >= 0) gone.push_back((uint32_t)s.to_local[g]);
+        if (!gone.empty()) SH_TRY(s, edynhip_remove_bodies(s.ctx, (uint32_t)gone.size(), gone.data()));
     }
     // gather and monitor buffers (sized by the context's capacity: they live as long as the context does)
     const size_t words = MonLayout(s.cap).words;
@@ -904,9 +955,16 @@ int rebuild(edynhip_world *w, const Carry &carry, bool from_state, const std::ve
 // body are read in full and rebuilt - the cost of an island meeting its neighbour follows the two shards involved, not the world
 // (round 5: a collapsing 262 144-box scene re-partitioned 18 times in 160 steps at 8 s each when every meeting rebuilt all shards from an
 // unrelated partition; scripts/multi_overhead.py).
-int repartition(edynhip_world *w, bool sticky) {
+// Edits of a running world come in with `edges` (body pairs that have to share a shard: a joint about to be made between two shards),
+// `force` (shards to rebuild whatever moves: one that needs a larger context) and from_edit: no step may have run since a shard was
+// built, so its device labels are not those of its islands - the labels it was built with stand in (the state has not moved since).
+int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint32_t, 2>> *edges = nullptr, const std::vector<uint8_t> *force = nullptr, bool from_edit = false) {
     const HostScene &sc = w->scene;
     const uint32_t n = sc.n, W = (uint32_t)w->shards.size();
+    // A body removed since the last step is its own island by the device labels (k_mark_removed) while its manifolds still tie it to its
+    // old one: only the full pass reads every manifold before it welds, so an edit that rebuilds shards in that state takes it (rare: a
+    // removal and a rebuilding edit with no step in between)
+    if (from_edit && !w->pending_tombs.empty()) sticky = false;
     PhaseTrace trace(w, sticky ? "sticky re-partition" : "full re-partition");
     w->pool->run([w, sticky](uint32_t r) { collect_shard(w, r, true, !sticky); });
     EH_TRY(shard_error(w));
@@ -934,6 +992,12 @@ int repartition(edynhip_world *w, bool sticky) {
             }
         }
     }
+    if (from_edit)
+        for (uint32_t r = 0; r < W; ++r) {
+            const Shard &s = w->shards[r];
+            if (!s.ctx || s.ctx->step_index != 0) continue;
+            for (uint32_t g : s.local_ids) if (w->rank_of[g] == (int32_t)r) labels[g] = w->query_labels.size() == n ? w->query_labels[g] : g;
+        }
     // the island query's labels: a shard that has not stepped since it was rebuilt still answers with the labels it was rebuilt with
     carry.island = labels;
     if (w->query_labels.size() == n)
@@ -991,7 +1055,8 @@ int repartition(edynhip_world *w, bool sticky) {
         const uint32_t ra = find(labels[a]), rb = find(labels[b]);
         if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
     };
-    for (uint32_t g = 0; g < sc.nj; ++g) unite(sc.jbody[2 * g], sc.jbody[2 * g + 1]);
+    for (uint32_t g = 0; g < sc.nj; ++g) if (sc.jalive[g]) unite(sc.jbody[2 * g], sc.jbody[2 * g + 1]);
+    if (edges) for (const auto &e : *edges) unite(e[0], e[1]);
     for (const edynhip_manifold &m : carry.manifolds) unite(m.body[0], m.body[1]);
     sweep_boxes(boxes, kCreationMargin, false, [&](const IslandBox &a, const IslandBox &b, float) {
         const uint32_t ra = find(a.label), rb = find(b.label);
@@ -1033,11 +1098,12 @@ int repartition(edynhip_world *w, bool sticky) {
         const uint32_t heaviest = *std::max_element(load.begin(), load.end());
         if (total >= 8 * W && (double)heaviest * W > 1.5 * (double)total) {
             ++w->stats.rebalances; --w->stats.repartitions;   // (counted again by the full pass)
-            return repartition(w, false);
+            return repartition(w, false, edges, nullptr, from_edit);
         }
     }
     std::vector<uint8_t> changed(W, 0);
     for (uint32_t i = 0; i < n; ++i) if (next[i] != w->rank_of[i]) { changed[(uint32_t)next[i]] = 1; changed[(uint32_t)w->rank_of[i]] = 1; }
+    if (force) for (uint32_t r = 0; r < W; ++r) if ((*force)[r]) changed[r] = 1;
     if (std::none_of(changed.begin(), changed.end(), [](uint8_t c) { return c != 0; })) {
         // nothing has to move (the close islands already share a shard): only the budget is taken again
         bool close = false;
@@ -1154,6 +1220,7 @@ int ensure_built(edynhip_world *w) {
         auto unite = [&](uint32_t a, uint32_t b) { const uint32_t ra = find(a), rb = find(b); if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb); };
         sweep_boxes(boxes, kCreationMargin, false, [&](const IslandBox &a, const IslandBox &b, float) { unite(a.label, b.label); });
         for (uint32_t g = 0; g < sc.nj; ++g) {
+            if (!sc.jalive[g]) continue;
             const uint32_t a = sc.jbody[2 * g], b = sc.jbody[2 * g + 1];
             if (sc.kind[a] == EDYNHIP_KIND_DYNAMIC && sc.kind[b] == EDYNHIP_KIND_DYNAMIC) unite(a, b);
         }
@@ -1292,7 +1359,8 @@ int edynhip_world_set_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies 
     copy_in(sc.inertia, in->has_inertia ? in->inertia : nullptr, 9 * (size_t)n); copy_in(sc.has_inertia, in->inertia ? in->has_inertia : nullptr, n);
     copy_in(sc.group, in->group, n); copy_in(sc.mask, in->mask, n); copy_in(sc.gravity, in->gravity, 3 * (size_t)n);
     copy_in(sc.sleeping_disabled, in->sleeping_disabled, n); copy_in(sc.com, in->center_of_mass, 3 * (size_t)n);
-    sc.nj = 0; sc.jtype.clear(); sc.jbody.clear(); sc.jpivot.clear(); sc.jaxis.clear(); sc.jparams.clear(); sc.defs.clear(); sc.exclusions.clear();
+    sc.nj = 0; sc.jtype.clear(); sc.jbody.clear(); sc.jpivot.clear(); sc.jaxis.clear(); sc.jparams.clear(); sc.jalive.clear(); sc.defs.clear(); sc.exclusions.clear();
+    w->removed.assign(n, 0); w->pending_tombs.clear();
     w->built = false; w->stepped = false;
     w->step_count = 0; w->ev_n = 0; w->ev_overflow = false;
     w->stats.num_bodies = n;
@@ -1302,8 +1370,8 @@ int edynhip_world_set_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies 
 int edynhip_world_set_joints(edynhip_world *w, uint32_t n, const edynhip_joints *in) {
     if (!w || (n && (!in || !in->type || !in->body || !in->pivot))) return EDYNHIP_ERR_INVALID;
     // The scene description is what the world is (re)built from - with the INITIAL state of edynhip_world_set_bodies. Once the world has
-    // stepped, such a rebuild would silently reset the simulation: refused (describe the scene again with edynhip_world_set_bodies -
-    // which takes the current state - as the C++ shim does for an edit of a running multi-device world)
+    // stepped, such a rebuild would silently reset the simulation: refused (a running world is edited through edynhip_world_add_joints,
+    // _remove_joints, _edit_joint, _edit_exclusion ... below; edynhip_world_set_bodies with the current state starts a new world)
     if (w->stepped) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_set_joints: the world has been stepped; describe the scene again (edynhip_world_set_bodies with the current state) before editing it");
     HostScene &sc = w->scene;
     for (uint32_t k = 0; k < 2 * n; ++k) if (in->body[k] >= sc.n) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_set_joints: body index out of range");
@@ -1311,6 +1379,7 @@ int edynhip_world_set_joints(edynhip_world *w, uint32_t n, const edynhip_joints 
     copy_in(sc.jtype, n ? in->type : nullptr, n); copy_in(sc.jbody, n ? in->body : nullptr, 2 * (size_t)n); copy_in(sc.jpivot, n ? in->pivot : nullptr, 6 * (size_t)n);
     if (n && in->axis) copy_in(sc.jaxis, in->axis, 6 * (size_t)n); else sc.jaxis.assign(6 * (size_t)n, 0.f);
     if (n && in->params) copy_in(sc.jparams, in->params, 10 * (size_t)n); else sc.jparams.assign(10 * (size_t)n, 0.f);
+    sc.jalive.assign(n, 1);
     sc.defs.clear();
     w->built = false;
     return EDYNHIP_OK;
@@ -1376,6 +1445,10 @@ int edynhip_world_step(edynhip_world *w, uint32_t nsteps) {
         EH_TRY(shard_error(w));
         ++w->stats.steps; ++w->step_count;
         w->stepped = true;
+        if (!w->pending_tombs.empty()) {   // the step dropped the removed bodies' manifolds: their slots are shapeless static bodies from here on
+            for (uint32_t g : w->pending_tombs) { w->scene.kind[g] = EDYNHIP_KIND_STATIC; w->scene.shape_type[g] = EDYNHIP_SHAPE_NONE; }
+            w->pending_tombs.clear();
+        }
         if (events) EH_TRY(append_events(w));
         if (w->shards.size() < 2) continue;
         float growth = 0.0f;
@@ -1409,6 +1482,7 @@ int edynhip_world_get_partition(edynhip_world *w, int32_t *rank_of) {
     if (!w || !rank_of) return EDYNHIP_ERR_INVALID;
     EH_TRY(ensure_built(w));
     std::memcpy(rank_of, w->rank_of.data(), w->scene.n * sizeof(int32_t));
+    for (uint32_t g = 0; g < w->scene.n; ++g) if (w->is_removed(g)) rank_of[g] = -1;   // a tombstone is nobody's
     return EDYNHIP_OK;
 }
 
@@ -1484,6 +1558,537 @@ int edynhip_world_debug_paths(edynhip_world *w, uint64_t *mask) {
 edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard) {
     if (!w || shard >= w->shards.size() || ensure_built(w) != EDYNHIP_OK) return nullptr;
     return w->shards[shard].ctx;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ edits of a running world
+// edynhip_world_add_bodies / _remove_bodies / _add_joints / _remove_joints / _edit_joint / _edit_exclusion / _set_state / _set_params:
+// the single context's edits in global indices. The scene (HostScene) stays the truth the shards are rebuilt from - bodies are appended,
+// a removed body becomes what the context itself turns the slot into (a shapeless static body), joints get an alive flag - and the
+// edit is forwarded to the context(s) that hold the bodies, so nobody else's manifolds, impulses, timers or point ids are touched.
+// The global-to-local maps stay ascending because a new body or joint has the highest global AND the highest local index.
+namespace {
+
+void scene_append_bodies(edynhip_world *w, uint32_t k, const edynhip_bodies *in) {
+    HostScene &sc = w->scene;
+    const size_t n0 = sc.n;
+    auto app = [&](auto &vec, const auto *src, size_t width) { vec.insert(vec.end(), src, src + (size_t)k * width); };
+    // an optional array the scene or the new bodies lack reads as its default there
+    auto opt = [&](auto &vec, const auto *src, size_t width, const auto *def_row) {
+        if (vec.empty() && !src) return;
+        if (vec.empty()) { vec.resize(n0 * width); for (size_t i = 0; i < vec.size(); ++i) vec[i] = def_row[i % width]; }
+        if (src) vec.insert(vec.end(), src, src + (size_t)k * width);
+        else for (size_t i = 0; i < (size_t)k * width; ++i) vec.push_back(def_row[i % width]);
+    };
+    app(sc.kind, in->kind, 1); app(sc.shape_type, in->shape_type, 1);
+    app(sc.pos, in->pos, 3); app(sc.orn, in->orn, 4); app(sc.linvel, in->linvel, 3); app(sc.angvel, in->angvel, 3);
+    app(sc.mass, in->mass, 1); app(sc.shape_param, in->shape_param, 4); app(sc.friction, in->friction, 1); app(sc.restitution, in->restitution, 1);
+    const bool own_inertia = in->inertia && in->has_inertia;
+    const float zeros[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const uint8_t zero8 = 0;
+    const uint64_t all = ~0ull;
+    opt(sc.inertia, own_inertia ? in->inertia : (const float *)nullptr, 9, zeros);
+    opt(sc.has_inertia, own_inertia ? in->has_inertia : (const uint8_t *)nullptr, 1, &zero8);
+    opt(sc.group, in->group, 1, &all); opt(sc.mask, in->mask, 1, &all);
+    opt(sc.gravity, in->gravity, 3, w->cfg.gravity);
+    opt(sc.sleeping_disabled, in->sleeping_disabled, 1, &zero8);
+    opt(sc.com, in->center_of_mass, 3, zeros);
+    sc.n += k;
+    w->removed.resize(sc.n, 0);
+    w->stats.num_bodies = sc.n;
+}
+
+void finish_tombstones(edynhip_world *w) {
+    for (uint32_t g : w->pending_tombs) { w->scene.kind[g] = EDYNHIP_KIND_STATIC; w->scene.shape_type[g] = EDYNHIP_SHAPE_NONE; }
+    w->pending_tombs.clear();
+}
+
+void scene_tombstones(edynhip_world *w, const std::vector<uint32_t> &gone) {
+    HostScene &sc = w->scene;
+    // A context keeps a removed body's manifolds until its next step drops them (with their destroy events). Until then the scene keeps
+    // the body as it was described, so that a shard rebuilt in between gets the body, its manifolds and their point ids as the old
+    // context held them and has the removal replayed on it (build_shard); the world's next step makes the slot what the context made of
+    // it for good: a shapeless static body (finish_tombstones).
+    for (uint32_t g : gone) { w->removed[g] = 1; w->pending_tombs.push_back(g); }
+    if (!w->built) finish_tombstones(w);
+    for (uint32_t j = 0; j < sc.nj; ++j) if (sc.jalive[j] && (w->removed[sc.jbody[2 * j]] || w->removed[sc.jbody[2 * j + 1]])) sc.jalive[j] = 0;
+    sc.exclusions.erase(std::remove_if(sc.exclusions.begin(), sc.exclusions.end(), [&](const std::array<uint32_t, 2> &e) { return w->removed[e[0]] || w->removed[e[1]]; }),
+                        sc.exclusions.end());
+}
+
+// radius of a sphere about the body's position that holds its shape (ensure_built's estimate); negative: no shape, touches nothing
+float bounding_radius(const HostScene &sc, int shape_type, const float *p, const float *com) {
+    float r = -1.0f;
+    switch (shape_type) {
+    case EDYNHIP_SHAPE_BOX: r = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]); break;
+    case EDYNHIP_SHAPE_SPHERE: r = p[0]; break;
+    case EDYNHIP_SHAPE_CAPSULE: r = p[0] + p[1]; break;
+    case EDYNHIP_SHAPE_CYLINDER: r = std::sqrt(p[0] * p[0] + p[1] * p[1]); break;
+    case EDYNHIP_SHAPE_POLYHEDRON: {
+        const size_t id = (size_t)p[0];
+        if (id >= sc.meshes.size()) return 0.0f;
+        const std::vector<float> &v = sc.meshes[id].v;
+        double c[3] = {0, 0, 0}, r2 = 0;
+        const size_t nv = v.size() / 3;
+        for (size_t i = 0; i < nv; ++i) for (int d = 0; d < 3; ++d) c[d] += v[3 * i + d];
+        for (int d = 0; d < 3; ++d) c[d] /= (double)std::max<size_t>(nv, 1);
+        for (size_t i = 0; i < nv; ++i) { double q = 0; for (int d = 0; d < 3; ++d) q += (v[3 * i + d] - c[d]) * (v[3 * i + d] - c[d]); r2 = std::max(r2, q); }
+        r = 2.0f * (float)std::sqrt(r2);
+        break;
+    }
+    default: return -1.0f;
+    }
+    if (com) r += std::sqrt(com[0] * com[0] + com[1] * com[1] + com[2] * com[2]);
+    return r;
+}
+
+// the shard that holds global joint j in its context (-1: none - a removed joint, or one between two replicated bodies) and its index there
+int32_t joint_shard(const edynhip_world *w, uint32_t j, uint32_t &local) {
+    for (uint32_t r = 0; r < w->shards.size(); ++r) {
+        const std::vector<uint32_t> &lj = w->shards[r].local_joints;
+        const auto it = std::lower_bound(lj.begin(), lj.end(), j);
+        if (it != lj.end() && *it == j) { local = (uint32_t)(it - lj.begin()); return (int32_t)r; }
+    }
+    return -1;
+}
+
+// the shard a joint between global bodies a and b lives on by build_shard's rule (-1: both replicated - no context holds it; -2: two shards)
+int32_t joint_home(const edynhip_world *w, uint32_t a, uint32_t b) {
+    const int32_t ra = w->scene.kind[a] == EDYNHIP_KIND_DYNAMIC ? w->rank_of[a] : -1, rb = w->scene.kind[b] == EDYNHIP_KIND_DYNAMIC ? w->rank_of[b] : -1;
+    if (ra >= 0 && rb >= 0) return ra == rb ? ra : -2;
+    return ra >= 0 ? ra : rb;
+}
+
+// Rebuilds the shards marked in `force` (each with the head-room its want_bodies / want_joints ask for) through what a sticky
+// re-partition carries; nothing else moves.
+int grow_shards(edynhip_world *w, const std::vector<uint8_t> &force) {
+    for (uint8_t f : force) if (f) ++w->edit_stats.shard_rebuilds;
+    return repartition(w, true, nullptr, &force, true);
+}
+
+// The safety condition after an edit that can bring islands of different shards together (a shaped dynamic body was added): the approach
+// check - body boxes while a shard has not stepped since it was built, island boxes otherwise; a new body is an island of its own either
+// way - which also records the boxes the growth monitor measures the new bodies against, and the sticky re-partition if it says "close".
+int edit_approach(edynhip_world *w, bool &moved) {
+    moved = false;
+    if (w->shards.size() < 2) return EDYNHIP_OK;
+    bool per_body = false;
+    for (const Shard &s : w->shards) if (s.ctx && !s.local_ids.empty() && s.ctx->step_index == 0) per_body = true;
+    bool close = false;
+    ++w->edit_stats.approach_checks_by_edit;
+    EH_TRY(approach_check(w, close, per_body));
+    if (!close) return EDYNHIP_OK;
+    moved = true;
+    ++w->edit_stats.repartitions_by_edit;
+    return repartition(w, true, nullptr, nullptr, true);
+}
+
+// the world's query tables of shard r after bodies [l0, nl) were appended to its context
+void shard_tables_appended(edynhip_world *w, uint32_t r, uint32_t l0) {
+    Shard &s = w->shards[r];
+    const uint32_t nl = (uint32_t)s.local_ids.size();
+    if (nl == l0) return;
+    SH_HIP(s, hipMemcpy(s.ids_dev + l0, s.local_ids.data() + l0, (size_t)(nl - l0) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    std::vector<uint32_t> bits;
+    if (r != 0) {
+        bits.assign((size_t)nl / 32 + 1, 0u);
+        for (uint32_t l : s.owned_local) bits[l >> 5] |= 1u << (l & 31u);
+        SH_HIP(s, hipMemcpy(s.ans_dev, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    const uint32_t *qisl = s.ctx->query_island;
+    if (qisl) {   // the labels the shard was built with still answer the island query: a new body is an island of its own
+        std::vector<uint32_t> own(nl - l0);
+        std::iota(own.begin(), own.end(), l0);
+        SH_HIP(s, hipMemcpy(s.qisl_dev + l0, own.data(), own.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    shard_set_answers(s.ctx, r != 0 ? s.ans_dev : nullptr, std::move(bits), qisl);
+}
+
+}  // namespace
+
+extern "C" {
+
+int edynhip_world_add_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies *in, uint32_t *first_index) {
+    if (!w) return EDYNHIP_ERR_INVALID;
+    HostScene &sc = w->scene;
+    if (first_index) *first_index = sc.n;
+    if (n == 0) return EDYNHIP_OK;
+    if (!in || !in->kind || !in->pos || !in->orn || !in->linvel || !in->angvel || !in->mass || !in->shape_type || !in->shape_param || !in->friction || !in->restitution)
+        return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_bodies: missing array");
+    if (sc.n == 0) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_bodies: describe the world first (edynhip_world_set_bodies)");
+    if ((uint64_t)sc.n + n > 0x7FFFFFFFull) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_add_bodies: too many bodies");
+    for (uint32_t k = 0; k < n; ++k) {
+        if (in->kind[k] < EDYNHIP_KIND_DYNAMIC || in->kind[k] > EDYNHIP_KIND_STATIC) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_bodies: unknown body kind");
+        if (in->shape_type[k] < EDYNHIP_SHAPE_NONE || in->shape_type[k] > EDYNHIP_SHAPE_POLYHEDRON) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_add_bodies: shape type");
+        if (in->shape_type[k] == EDYNHIP_SHAPE_POLYHEDRON && !(in->shape_param[4 * (size_t)k] >= 0 && (size_t)in->shape_param[4 * (size_t)k] < sc.meshes.size()))
+            return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_bodies: a polyhedron refers to a mesh the world does not hold");
+    }
+    const uint32_t n0 = sc.n, W = (uint32_t)w->shards.size();
+    if (!w->built) { scene_append_bodies(w, n, in); return EDYNHIP_OK; }
+    ++w->edit_stats.edits;
+    // placement: replicated, or the shard with the fewest live dynamic bodies (ties: the lowest shard), one new body after the other in
+    // index order - and with a body every later body of the call that it touches, directly or through others (the boxes of their
+    // bounding spheres within the creation margin): a pile spawned in one call lands on one shard instead of being welded together there
+    std::vector<uint32_t> load(W, 0), extra(W, 0);
+    for (uint32_t g = 0; g < n0; ++g) if (sc.kind[g] == EDYNHIP_KIND_DYNAMIC && !w->is_removed(g) && w->rank_of[g] >= 0) ++load[(uint32_t)w->rank_of[g]];
+    std::vector<int32_t> place(n, -1);
+    bool shaped_dynamic = false;
+    std::vector<uint32_t> group(n);
+    std::iota(group.begin(), group.end(), 0u);
+    {
+        std::vector<IslandBox> boxes;
+        for (uint32_t k = 0; k < n; ++k) {
+            if (in->kind[k] != EDYNHIP_KIND_DYNAMIC) continue;
+            const float r = bounding_radius(sc, in->shape_type[k], in->shape_param + 4 * (size_t)k, in->center_of_mass ? in->center_of_mass + 3 * (size_t)k : nullptr);
+            if (r < 0) continue;
+            IslandBox b;
+            for (int d = 0; d < 3; ++d) { b.lo[d] = in->pos[3 * (size_t)k + d] - r; b.hi[d] = in->pos[3 * (size_t)k + d] + r; }
+            b.label = k; b.owner = 0;
+            boxes.push_back(b);
+        }
+        auto find = [&](uint32_t x) { while (group[x] != x) { group[x] = group[group[x]]; x = group[x]; } return x; };
+        sweep_boxes(boxes, kCreationMargin, false, [&](const IslandBox &a, const IslandBox &b, float) {
+            const uint32_t ra = find(a.label), rb = find(b.label);
+            if (ra != rb) group[std::max(ra, rb)] = std::min(ra, rb);
+        });
+        for (uint32_t k = 0; k < n; ++k) group[k] = find(k);   // (the root is the group's lowest index: placed before its members)
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        if (in->kind[k] != EDYNHIP_KIND_DYNAMIC) { for (uint32_t r = 0; r < W; ++r) ++extra[r]; continue; }
+        uint32_t r = 0;
+        if (group[k] != k) r = (uint32_t)place[group[k]];
+        else for (uint32_t q = 1; q < W; ++q) if (load[q] < load[r]) r = q;
+        place[k] = (int32_t)r; ++load[r]; ++extra[r];
+        if (in->shape_type[k] != EDYNHIP_SHAPE_NONE) shaped_dynamic = true;
+    }
+    // a shard whose context cannot take its share is rebuilt with head-room first, through the carry
+    bool grown = false;
+    {
+        std::vector<uint8_t> force(W, 0);
+        for (uint32_t r = 0; r < W; ++r) {
+            Shard &s = w->shards[r];
+            if (extra[r] && (!s.ctx || s.local_ids.size() + extra[r] > s.cap)) { force[r] = 1; s.want_bodies = extra[r]; grown = true; }
+        }
+        if (grown) {
+            EH_TRY(grow_shards(w, force));
+            for (uint32_t r = 0; r < W; ++r)
+                if (extra[r] && (!w->shards[r].ctx || w->shards[r].local_ids.size() + extra[r] > w->shards[r].cap))
+                    return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_bodies: shard " + std::to_string(r) + " was rebuilt and still lacks room");
+        }
+    }
+    scene_append_bodies(w, n, in);
+    for (uint32_t k = 0; k < n; ++k) w->rank_of.push_back(place[k]);
+    w->pos.insert(w->pos.end(), in->pos, in->pos + 3 * (size_t)n); w->orn.insert(w->orn.end(), in->orn, in->orn + 4 * (size_t)n);
+    w->linvel.insert(w->linvel.end(), in->linvel, in->linvel + 3 * (size_t)n); w->angvel.insert(w->angvel.end(), in->angvel, in->angvel + 3 * (size_t)n);
+    if (w->query_labels.size() == n0) for (uint32_t k = 0; k < n; ++k) w->query_labels.push_back(n0 + k);
+    w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        s.rc = EDYNHIP_OK; s.err.clear();
+        s.to_local.resize((size_t)n0 + n, -1);
+        std::vector<uint32_t> mine;
+        for (uint32_t k = 0; k < n; ++k) if (place[k] == (int32_t)r || place[k] < 0) mine.push_back(k);
+        if (mine.empty()) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        const BodyRows sub(*in, mine);
+        const edynhip_bodies b = sub.view();
+        SH_TRY(s, edynhip_add_bodies(s.ctx, (uint32_t)mine.size(), &b));
+        const uint32_t l0 = (uint32_t)s.local_ids.size();
+        for (uint32_t k : mine) {
+            const uint32_t l = (uint32_t)s.local_ids.size();
+            s.to_local[n0 + k] = (int32_t)l;
+            if (place[k] == (int32_t)r || r == 0) s.owned_local.push_back(l);
+            s.local_ids.push_back(n0 + k);
+        }
+        shard_tables_appended(w, r, l0);
+        if (s.rc != EDYNHIP_OK) return;
+        gather_shard(w, r, false);   // the state the context holds for them (the centre of mass where the caller gave an origin)
+    });
+    EH_TRY(shard_error(w));
+    for (uint32_t r = 0; r < W; ++r) w->stats.bodies_per_shard[r < 16 ? r : 15] = (uint32_t)w->shards[r].owned_local.size();
+    bool moved = false;
+    if (shaped_dynamic) EH_TRY(edit_approach(w, moved));
+    if (!grown && !moved) ++w->edit_stats.in_place;
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_remove_bodies(edynhip_world *w, uint32_t n, const uint32_t *indices) {
+    if (!w || (n && !indices)) return EDYNHIP_ERR_INVALID;
+    HostScene &sc = w->scene;
+    for (uint32_t k = 0; k < n; ++k) if (indices[k] >= sc.n) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_remove_bodies: index out of range");
+    std::vector<uint32_t> gone;
+    for (uint32_t k = 0; k < n; ++k) if (!w->is_removed(indices[k]) && std::find(gone.begin(), gone.end(), indices[k]) == gone.end()) gone.push_back(indices[k]);
+    if (gone.empty()) return EDYNHIP_OK;
+    w->removed.resize(sc.n, 0);
+    if (w->built) {
+        ++w->edit_stats.edits;
+        w->pool->run([&](uint32_t r) {   // the owner of a dynamic body, every shard for a replicated one
+            Shard &s = w->shards[r];
+            s.rc = EDYNHIP_OK; s.err.clear();
+            std::vector<uint32_t> mine;
+            for (uint32_t g : gone) if (g < s.to_local.size() && s.to_local[g] >= 0) mine.push_back((uint32_t)s.to_local[g]);
+            if (mine.empty() || !s.ctx) return;
+            SH_HIP(s, hipSetDevice(s.device));
+            SH_TRY(s, edynhip_remove_bodies(s.ctx, (uint32_t)mine.size(), mine.data()));
+        });
+        EH_TRY(shard_error(w));
+        ++w->edit_stats.in_place;
+    }
+    scene_tombstones(w, gone);
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_add_joints(edynhip_world *w, uint32_t n, const edynhip_joints *in, uint32_t *first_index) {
+    if (!w) return EDYNHIP_ERR_INVALID;
+    HostScene &sc = w->scene;
+    if (first_index) *first_index = sc.nj;
+    if (n == 0) return EDYNHIP_OK;
+    if (!in || !in->type || !in->body || !in->pivot) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_joints: missing array");
+    for (uint32_t e = 0; e < n; ++e) {
+        const uint32_t a = in->body[2 * e], b = in->body[2 * e + 1];
+        if (a >= sc.n || b >= sc.n) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_joints: body index out of range");
+        // (a null constraint has no rows: it may name any slot - a caller reserves a joint index with one, as the C++ shim does)
+        if (in->type[e] != EDYNHIP_JOINT_NULL && (w->is_removed(a) || w->is_removed(b))) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_joints: joint " + std::to_string(e) + " names a removed body");
+        if (in->type[e] < EDYNHIP_JOINT_POINT || in->type[e] > EDYNHIP_JOINT_NULL) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_add_joints: joint type");
+        if (in->type[e] == EDYNHIP_JOINT_HINGE && !in->axis) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_joints: hinge needs axes");
+    }
+    const uint32_t nj0 = sc.nj, W = (uint32_t)w->shards.size();
+    auto append_scene = [&] {
+        sc.jtype.insert(sc.jtype.end(), in->type, in->type + n); sc.jbody.insert(sc.jbody.end(), in->body, in->body + 2 * (size_t)n);
+        sc.jpivot.insert(sc.jpivot.end(), in->pivot, in->pivot + 6 * (size_t)n);
+        if (in->axis) sc.jaxis.insert(sc.jaxis.end(), in->axis, in->axis + 6 * (size_t)n); else sc.jaxis.resize(sc.jaxis.size() + 6 * (size_t)n, 0.f);
+        if (in->params) sc.jparams.insert(sc.jparams.end(), in->params, in->params + 10 * (size_t)n); else sc.jparams.resize(sc.jparams.size() + 10 * (size_t)n, 0.f);
+        sc.jalive.resize((size_t)nj0 + n, 1);
+        sc.nj = nj0 + n;
+    };
+    if (!w->built) { append_scene(); return EDYNHIP_OK; }
+    ++w->edit_stats.edits;
+    // a joint between two shards: its islands move together first (the welding unites the pair), then the joint is made in place
+    bool moved = false;
+    {
+        std::vector<std::array<uint32_t, 2>> edges;
+        for (uint32_t e = 0; e < n; ++e) if (joint_home(w, in->body[2 * e], in->body[2 * e + 1]) == -2) edges.push_back({in->body[2 * e], in->body[2 * e + 1]});
+        if (!edges.empty()) {
+            moved = true;
+            ++w->edit_stats.repartitions_by_edit;
+            EH_TRY(repartition(w, true, &edges, nullptr, true));
+            for (const auto &e : edges) if (joint_home(w, e[0], e[1]) == -2) return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: the re-partition left a joint's bodies on two shards");
+        }
+    }
+    std::vector<int32_t> home(n);
+    std::vector<uint32_t> extra(W, 0);
+    for (uint32_t e = 0; e < n; ++e) { home[e] = joint_home(w, in->body[2 * e], in->body[2 * e + 1]); if (home[e] >= 0) ++extra[(uint32_t)home[e]]; }
+    bool grown = false;
+    {
+        std::vector<uint8_t> force(W, 0);
+        for (uint32_t r = 0; r < W; ++r) {
+            Shard &s = w->shards[r];
+            if (extra[r] && (!s.ctx || s.local_joints.size() + extra[r] > s.joint_cap)) { force[r] = 1; s.want_joints = extra[r]; grown = true; }
+        }
+        if (grown) {
+            EH_TRY(grow_shards(w, force));
+            for (uint32_t e = 0; e < n; ++e) home[e] = joint_home(w, in->body[2 * e], in->body[2 * e + 1]);   // (a rebalance may have moved islands)
+            std::fill(extra.begin(), extra.end(), 0u);
+            for (uint32_t e = 0; e < n; ++e) { if (home[e] == -2) return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: a joint's bodies are on two shards"); if (home[e] >= 0) ++extra[(uint32_t)home[e]]; }
+            for (uint32_t r = 0; r < W; ++r)
+                if (extra[r] && w->shards[r].local_joints.size() + extra[r] > w->shards[r].joint_cap)
+                    return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: shard " + std::to_string(r) + " was rebuilt and still lacks room");
+        }
+    }
+    w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        s.rc = EDYNHIP_OK; s.err.clear();
+        std::vector<uint32_t> mine;
+        for (uint32_t e = 0; e < n; ++e) if (home[e] == (int32_t)r) mine.push_back(e);
+        if (mine.empty()) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        auto jt = rows_of(in->type, mine, 1);
+        auto jb = rows_of(in->body, mine, 2);
+        for (uint32_t &x : jb) x = (uint32_t)s.to_local[x];
+        auto jp = rows_of(in->pivot, mine, 6), ja = rows_of(in->axis, mine, 6), jq = rows_of(in->params, mine, 10);
+        edynhip_joints j{};
+        j.type = jt.data(); j.body = jb.data(); j.pivot = jp.data(); j.axis = ja.empty() ? nullptr : ja.data(); j.params = jq.empty() ? nullptr : jq.data();
+        uint32_t first = 0;
+        SH_TRY(s, edynhip_add_joints(s.ctx, (uint32_t)mine.size(), &j, &first));
+        if (first != s.local_joints.size()) { s.rc = EDYNHIP_ERR_INTERNAL; s.err = "the context's joint indices and the shard's joint map disagree"; return; }
+        for (uint32_t e : mine) s.local_joints.push_back(nj0 + e);
+    });
+    EH_TRY(shard_error(w));
+    append_scene();
+    if (!grown && !moved) ++w->edit_stats.in_place;
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_remove_joints(edynhip_world *w, uint32_t n, const uint32_t *indices) {
+    if (!w || (n && !indices)) return EDYNHIP_ERR_INVALID;
+    HostScene &sc = w->scene;
+    for (uint32_t k = 0; k < n; ++k) if (indices[k] >= sc.nj) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_remove_joints: index out of range");
+    std::vector<uint32_t> gone;
+    for (uint32_t k = 0; k < n; ++k) if (sc.jalive[indices[k]] && std::find(gone.begin(), gone.end(), indices[k]) == gone.end()) gone.push_back(indices[k]);
+    if (gone.empty()) return EDYNHIP_OK;
+    if (w->built) {
+        ++w->edit_stats.edits;
+        std::vector<std::vector<uint32_t>> mine(w->shards.size());
+        for (uint32_t j : gone) { uint32_t l = 0; const int32_t r = joint_shard(w, j, l); if (r >= 0) mine[(uint32_t)r].push_back(l); }
+        w->pool->run([&](uint32_t r) {
+            Shard &s = w->shards[r];
+            s.rc = EDYNHIP_OK; s.err.clear();
+            if (mine[r].empty()) return;
+            SH_HIP(s, hipSetDevice(s.device));
+            SH_TRY(s, edynhip_remove_joints(s.ctx, (uint32_t)mine[r].size(), mine[r].data()));
+        });
+        EH_TRY(shard_error(w));
+        ++w->edit_stats.in_place;
+    }
+    for (uint32_t j : gone) sc.jalive[j] = 0;
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_edit_joint(edynhip_world *w, uint32_t joint, const float *frame_a9, const float *frame_b9, const float *params, int generic) {
+    if (!w) return EDYNHIP_ERR_INVALID;
+    HostScene &sc = w->scene;
+    if (!params || generic < -1 || generic > 1 || (generic >= 0 && (!frame_a9 || !frame_b9))) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: missing array");
+    if (joint >= sc.nj) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: joint index out of range");
+    if (!sc.jalive[joint]) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: the joint has been removed");
+    const int t = sc.jtype[joint];
+    if (generic == 0 && t != EDYNHIP_JOINT_CONE && t != EDYNHIP_JOINT_CVJOINT) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: cone and cvjoint constraints only");
+    if (generic == 0 && t == EDYNHIP_JOINT_CONE && !(params[0] > 0 && params[1] > 0)) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: cone span tangents must be positive");
+    if (generic == 1 && t != EDYNHIP_JOINT_GENERIC) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: generic constraints only");
+    if (generic == 1) for (int d = 0; d < 6; ++d) if (params[10 * d] != 0 && params[10 * d + 1] > params[10 * d + 2]) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_joint: a limit's minimum exceeds its maximum");
+    if (w->built) {
+        ++w->edit_stats.edits;
+        uint32_t l = 0;
+        const int32_t r = joint_shard(w, joint, l);
+        if (r >= 0) {
+            Shard &s = w->shards[(uint32_t)r];
+            W_HIP(w, hipSetDevice(s.device));
+            const int rc = generic < 0 ? edynhip_set_joint_params(s.ctx, l, params) : (generic ? edynhip_set_generic_definition(s.ctx, l, frame_a9, frame_b9, params) : edynhip_set_joint_definition(s.ctx, l, frame_a9, frame_b9, params));
+            if (rc != EDYNHIP_OK) return w->fail(rc, std::string("edynhip_world_edit_joint: shard ") + std::to_string(r) + ": " + edynhip_last_error(s.ctx));
+        }
+        ++w->edit_stats.in_place;
+    }
+    if (generic < 0) { std::memcpy(&sc.jparams[10 * (size_t)joint], params, 10 * sizeof(float)); return EDYNHIP_OK; }
+    HostScene::Def d;
+    d.joint = joint; d.generic = generic != 0;
+    d.fa.assign(frame_a9, frame_a9 + 9); d.fb.assign(frame_b9, frame_b9 + 9); d.p.assign(params, params + (generic ? 60 : 16));
+    for (HostScene::Def &old : sc.defs) if (old.joint == joint && old.generic == d.generic) { old = std::move(d); return EDYNHIP_OK; }
+    sc.defs.push_back(std::move(d));
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_edit_exclusion(edynhip_world *w, uint32_t a, uint32_t b, int exclude) {
+    if (!w) return EDYNHIP_ERR_INVALID;
+    HostScene &sc = w->scene;
+    if (a >= sc.n || b >= sc.n) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_exclusion: body index out of range");
+    if (a == b) return exclude ? w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_edit_exclusion: a body cannot exclude itself") : (int)EDYNHIP_OK;
+    if (w->is_removed(a) || w->is_removed(b)) return EDYNHIP_OK;   // (a tombstone collides with nothing)
+    auto same = [&](const std::array<uint32_t, 2> &e) { return (e[0] == a && e[1] == b) || (e[0] == b && e[1] == a); };
+    const bool listed = std::any_of(sc.exclusions.begin(), sc.exclusions.end(), same);
+    if (exclude && !listed) {
+        uint32_t na = 0, nb = 0;
+        for (const auto &e : sc.exclusions) { if (e[0] == a || e[1] == a) ++na; if (e[0] == b || e[1] == b) ++nb; }
+        if (na >= 16 || nb >= 16) return w->fail(EDYNHIP_ERR_CAPACITY, "edynhip_world_edit_exclusion: more than 16 exclusions on one body (collision_exclusion::max_exclusions)");
+    }
+    if (w->built) {
+        ++w->edit_stats.edits;
+        for (uint32_t r = 0; r < w->shards.size(); ++r) {   // the shard build_shard gives the pair to; a pair on two shards is the scene's until its bodies meet
+            Shard &s = w->shards[r];
+            if (!s.ctx || s.to_local[a] < 0 || s.to_local[b] < 0 || !(w->rank_of[a] == (int32_t)r || w->rank_of[b] == (int32_t)r)) continue;
+            W_HIP(w, hipSetDevice(s.device));
+            const int rc = exclude ? edynhip_exclude_collision(s.ctx, (uint32_t)s.to_local[a], (uint32_t)s.to_local[b]) : edynhip_remove_collision_exclusion(s.ctx, (uint32_t)s.to_local[a], (uint32_t)s.to_local[b]);
+            if (rc != EDYNHIP_OK) return w->fail(rc, std::string("edynhip_world_edit_exclusion: shard ") + std::to_string(r) + ": " + edynhip_last_error(s.ctx));
+        }
+        ++w->edit_stats.in_place;
+    }
+    if (exclude) { if (!listed) sc.exclusions.push_back({a, b}); }
+    else sc.exclusions.erase(std::remove_if(sc.exclusions.begin(), sc.exclusions.end(), same), sc.exclusions.end());
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_set_state(edynhip_world *w, const float *pos, const float *orn, const float *linvel, const float *angvel) {
+    if (!w) return EDYNHIP_ERR_INVALID;
+    if (!pos || !orn || !linvel || !angvel) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_set_state: missing array");
+    HostScene &sc = w->scene;
+    const size_t n = sc.n;
+    if (n == 0) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_set_state: no bodies");
+    if (!w->built && sc.com.empty()) {   // the description's state (with centre-of-mass offsets `pos` is no longer the origin it describes: build first)
+        sc.pos.assign(pos, pos + 3 * n); sc.orn.assign(orn, orn + 4 * n); sc.linvel.assign(linvel, linvel + 3 * n); sc.angvel.assign(angvel, angvel + 3 * n);
+        return EDYNHIP_OK;
+    }
+    EH_TRY(ensure_built(w));
+    ++w->edit_stats.edits;
+    w->pos.assign(pos, pos + 3 * n); w->orn.assign(orn, orn + 4 * n); w->linvel.assign(linvel, linvel + 3 * n); w->angvel.assign(angvel, angvel + 3 * n);
+    w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        s.rc = EDYNHIP_OK; s.err.clear();
+        if (s.local_ids.empty() || !s.ctx) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        auto p = take(w->pos, s.local_ids, 3), q = take(w->orn, s.local_ids, 4), v = take(w->linvel, s.local_ids, 3), o = take(w->angvel, s.local_ids, 3);
+        SH_TRY(s, edynhip_set_state(s.ctx, p.data(), q.data(), v.data(), o.data()));
+    });
+    EH_TRY(shard_error(w));
+    // A context's boxes follow the new state at the end of its next step (edynhip_set_state), which is when its broadphase - and the growth
+    // monitor - first see where the bodies went: the approach check is due right after that step, whatever the budget said before.
+    w->budget = 0.0f;
+    ++w->edit_stats.in_place;
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_get_params(edynhip_world *w, edynhip_params *out) {
+    if (!w || !out) return EDYNHIP_ERR_INVALID;
+    if (w->built && !w->shards.empty() && w->shards[0].ctx) return edynhip_get_params(w->shards[0].ctx, out);
+    if (w->params_set) { *out = w->params; return EDYNHIP_OK; }
+    out->fixed_dt = w->cfg.fixed_dt > 0 ? w->cfg.fixed_dt : 1.0f / 60.0f;
+    out->num_velocity_iterations = w->cfg.num_velocity_iterations; out->num_position_iterations = w->cfg.num_position_iterations;
+    std::memcpy(out->gravity, w->cfg.gravity, sizeof(out->gravity));
+    out->num_restitution_iterations = 8; out->num_individual_restitution_iterations = 3;   // settings.hpp:28-29, as a context starts
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_set_params(edynhip_world *w, const edynhip_params *p) {
+    if (!w) return EDYNHIP_ERR_INVALID;
+    if (!p || !(p->fixed_dt > 0)) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_set_params: bad settings");
+    HostScene &sc = w->scene;
+    if (w->built) {
+        ++w->edit_stats.edits;
+        for (uint32_t r = 0; r < w->shards.size(); ++r) {
+            Shard &s = w->shards[r];
+            if (!s.ctx) continue;
+            const int rc = edynhip_set_params(s.ctx, p);
+            if (rc != EDYNHIP_OK) return w->fail(rc, std::string("edynhip_world_set_params: shard ") + std::to_string(r) + ": " + edynhip_last_error(s.ctx));
+        }
+        ++w->edit_stats.in_place;
+    }
+    // what later contexts are created with: set_gravity replaces the gravity of every dynamic body (gravity_util.cpp:12-20)
+    if (std::memcmp(w->cfg.gravity, p->gravity, sizeof(p->gravity)) != 0 && !sc.gravity.empty())
+        for (uint32_t g = 0; g < sc.n; ++g) if (sc.kind[g] == EDYNHIP_KIND_DYNAMIC) std::memcpy(&sc.gravity[3 * (size_t)g], p->gravity, sizeof(p->gravity));
+    w->params = *p; w->params_set = true;
+    w->cfg.fixed_dt = p->fixed_dt; w->cfg.num_velocity_iterations = p->num_velocity_iterations; w->cfg.num_position_iterations = p->num_position_iterations;
+    std::memcpy(w->cfg.gravity, p->gravity, sizeof(p->gravity));
+    return EDYNHIP_OK;
+}
+
+int edynhip_world_get_asleep(edynhip_world *w, uint8_t *asleep) {
+    if (!w || !asleep) return EDYNHIP_ERR_INVALID;
+    EH_TRY(ensure_built(w));
+    std::memset(asleep, 0, w->scene.n);
+    if (!(w->cfg.flags & EDYNHIP_FLAG_SLEEPING)) return EDYNHIP_OK;
+    w->pool->run([&](uint32_t r) {   // every body's tag from the shard that reports its state
+        Shard &s = w->shards[r];
+        s.rc = EDYNHIP_OK; s.err.clear();
+        if (s.local_ids.empty() || !s.ctx) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        s.asleep.assign(s.local_ids.size(), 0);
+        SH_TRY(s, edynhip_get_asleep(s.ctx, s.asleep.data()));
+        for (uint32_t l : s.owned_local) asleep[s.local_ids[l]] = s.asleep[l];
+    });
+    return shard_error(w);
+}
+
+int edynhip_world_get_edit_stats(edynhip_world *w, edynhip_world_edit_stats *out) {
+    if (!w || !out) return EDYNHIP_ERR_INVALID;
+    *out = w->edit_stats;
+    return EDYNHIP_OK;
 }
 
 }  // extern "C"

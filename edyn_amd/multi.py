@@ -35,6 +35,7 @@ class MultiWorld:
         self._h = C.c_void_p(h)
         self.num_shards = len(dev)
         self.n = 0
+        self.nj = 0
 
     def close(self):
         if self._h:
@@ -75,6 +76,110 @@ class MultiWorld:
             self._check(self._L.edynhip_world_set_joint_definition(self._h, int(j), _ptr(fa), _ptr(fb), _ptr(q), 0))
         for a, bb in scene.get("exclusions", []):
             self._check(self._L.edynhip_world_exclude_collision(self._h, int(a), int(bb)))
+
+    # ---- edits of a running world: what World.add_scene / remove_bodies / add_joints ... do on one context, in global indices
+    def add_scene(self, scene):
+        """Append the bodies, joints (with `hinge_params`), `joint_defs` and `exclusions` of `scene` - indices relative to the scene - to
+        the world, running or not; everybody else's manifolds, impulses, timers and point ids are kept. Returns (first_body, first_joint)."""
+        n, keep, b = World._body_arrays(None, scene)
+        first = C.c_uint32(0)
+        self._check(self._L.edynhip_world_add_bodies(self._h, n, C.byref(b), C.byref(first)))
+        self.n += n
+        fb = first.value
+        fj = self.nj
+        joints = scene.get("joints") or []
+        if joints:
+            joints = [(j[0], j[1] + fb, j[2] + fb) + tuple(j[3:]) for j in joints]
+            fj = self.add_joints(joints, hinge_params=scene.get("hinge_params", []))
+        for j, fa, fbm, p in scene.get("joint_defs", []):
+            self.set_joint_definition(fj + int(j), fa, fbm, p)
+        for a, bb in scene.get("exclusions", []):
+            self.exclude_collision(fb + int(a), fb + int(bb))
+        return fb, fj
+
+    def remove_bodies(self, indices):
+        """registry.destroy(rigid body): the indices stay reserved, the bodies' joints go with them (edynhip_world_remove_bodies)."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self._L.edynhip_world_remove_bodies(self._h, len(idx), _ptr(idx)))
+
+    def add_joints(self, joints, hinge_params=()):
+        """Append joints (World.add_joints' tuples, global body indices; hinge_params: (index in `joints`, params) rows). Returns the first new index."""
+        (jt, jb, jp, ja, jq), js = World._joint_arrays(joints)
+        for j, p in hinge_params:
+            jq[j, :len(p)] = p
+        first = C.c_uint32(0)
+        self._check(self._L.edynhip_world_add_joints(self._h, len(joints), C.byref(js), C.byref(first)))
+        self.nj += len(joints)
+        return first.value
+
+    def remove_joints(self, indices):
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self._L.edynhip_world_remove_joints(self._h, len(idx), _ptr(idx)))
+
+    def set_joint_params(self, joint, params):
+        p = np.zeros(10, np.float32); p[:len(params)] = params
+        self._check(self._L.edynhip_world_edit_joint(self._h, int(joint), None, None, _ptr(p), -1))
+
+    def set_joint_definition(self, joint, frameA, frameB, params):
+        p = np.zeros(16, np.float32); p[:len(params)] = params
+        fa = np.ascontiguousarray(np.asarray(frameA, np.float32).reshape(9)); fb = np.ascontiguousarray(np.asarray(frameB, np.float32).reshape(9))
+        self._check(self._L.edynhip_world_edit_joint(self._h, int(joint), _ptr(fa), _ptr(fb), _ptr(p), 0))
+
+    def set_generic_definition(self, joint, frameA, frameB, dofs):
+        p = np.ascontiguousarray(np.asarray(dofs, np.float32).reshape(60))
+        fa = np.ascontiguousarray(np.asarray(frameA, np.float32).reshape(9)); fb = np.ascontiguousarray(np.asarray(frameB, np.float32).reshape(9))
+        self._check(self._L.edynhip_world_edit_joint(self._h, int(joint), _ptr(fa), _ptr(fb), _ptr(p), 1))
+
+    def exclude_collision(self, a, b):
+        self._check(self._L.edynhip_world_edit_exclusion(self._h, int(a), int(b), 1))
+
+    def remove_collision_exclusion(self, a, b):
+        self._check(self._L.edynhip_world_edit_exclusion(self._h, int(a), int(b), 0))
+
+    def set_state(self, pos, orn, lv, av):
+        p = np.ascontiguousarray(pos, np.float32); q = np.ascontiguousarray(orn, np.float32)
+        v = np.ascontiguousarray(lv, np.float32); o = np.ascontiguousarray(av, np.float32)
+        if (p.size, q.size, v.size, o.size) != (3 * self.n, 4 * self.n, 3 * self.n, 3 * self.n):
+            raise ValueError("set_state takes the state of every body of the world")
+        self._check(self._L.edynhip_world_set_state(self._h, _ptr(p), _ptr(q), _ptr(v), _ptr(o)))
+
+    def get_params(self):
+        p = _capi.Params()
+        self._check(self._L.edynhip_world_get_params(self._h, C.byref(p)))
+        return {"fixed_dt": p.fixed_dt, "velocity_iterations": p.num_velocity_iterations, "position_iterations": p.num_position_iterations,
+                "gravity": tuple(p.gravity), "restitution_iterations": p.num_restitution_iterations,
+                "individual_restitution_iterations": p.num_individual_restitution_iterations}
+
+    def set_params(self, fixed_dt=None, velocity_iterations=None, position_iterations=None, gravity=None,
+                   restitution_iterations=None, individual_restitution_iterations=None):
+        """World.set_params on the whole world: no contact state is lost (edynhip_world_set_params)."""
+        p = _capi.Params()
+        self._check(self._L.edynhip_world_get_params(self._h, C.byref(p)))
+        if fixed_dt is not None:
+            p.fixed_dt = fixed_dt
+        if velocity_iterations is not None:
+            p.num_velocity_iterations = velocity_iterations
+        if position_iterations is not None:
+            p.num_position_iterations = position_iterations
+        if gravity is not None:
+            p.gravity = (C.c_float * 3)(*[float(x) for x in gravity])
+        if restitution_iterations is not None:
+            p.num_restitution_iterations = restitution_iterations
+        if individual_restitution_iterations is not None:
+            p.num_individual_restitution_iterations = individual_restitution_iterations
+        self._check(self._L.edynhip_world_set_params(self._h, C.byref(p)))
+
+    def get_asleep(self):
+        """World.get_asleep on the whole world: one flag per body, global order (edynhip_world_get_asleep)."""
+        out = np.zeros(self.n, np.uint8)
+        self._check(self._L.edynhip_world_get_asleep(self._h, _ptr(out)))
+        return out
+
+    def get_edit_stats(self):
+        """Which path the edits took (edynhip_world_edit_stats): edits, in_place, shard_rebuilds, repartitions_by_edit, approach_checks_by_edit."""
+        st = _capi.WorldEditStats()
+        self._check(self._L.edynhip_world_get_edit_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _capi.WorldEditStats._fields_}
 
     def set_should_collide(self, func):
         """edyn::set_should_collide on a world over several devices: func(body, other) -> bool with GLOBAL body indices replaces

@@ -244,8 +244,12 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
     // islands partitioned by load, re-partitioned when islands of different shards meet) - the reference's island parallelism
     // (solver.cpp:408-428) across devices. Bodies of every shape, every constraint type, exclusions and settings are supported;
     // contact entities, contact_extras materials / the mix table, asynchronous mode and step callbacks are single-device features
-    // (attach throws stepper_error EDYNHIP_ERR_UNSUPPORTED when combined); an edit of a running multi-device world (bodies made or
-    // destroyed, edyn::refresh) rebuilds the world from the registry - correct, but the contacts' warm start is lost.
+    // (attach throws stepper_error EDYNHIP_ERR_UNSUPPORTED when combined). An edit of a running multi-device world is forwarded to
+    // the world as it is to one context (edynhip.h "Edits of a RUNNING multi-device world"): bodies and constraints made after attach,
+    // their definitions, exclude_collision, registry.destroy of either, edyn::refresh and settings changes keep every contact's warm
+    // start, the joints' impulses and angles, sleep timers and the step count - the registry program computes what it computes on one
+    // device, bit for bit. What the single-device path also answers with a fresh upload (a shape, kind, mass or material edit, a
+    // convex mesh first seen after the bodies went up) still rebuilds the world from the registry.
     std::vector<int> devices{};
     unsigned max_bodies{0};      // 0 = sized at the first upload (count + 25 % head-room)
     unsigned max_manifolds{0};
@@ -681,8 +685,9 @@ inline void upload_joint_defs(entt::registry &registry, gpu_stepper &s, uint32_t
     }
 }
 
-// init_config::devices names several GPUs: the whole scene goes to the multi-GPU world (edynhip_world_*), which takes a scene once -
-// so every (re)upload builds a new world from the registry's current components.
+// init_config::devices names several GPUs: the whole scene goes to the multi-GPU world (edynhip_world_*). This is the full upload - the
+// first one, and the answer to edits that re-create a single context too (s.recreate): a new world from the registry's current components.
+// Everything else is appended to / edited on the running world (append_scene_multi, upload_state_multi, apply_params_multi, sync_removed).
 inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     const uint32_t total = (uint32_t)s.bodies.size(), nj = (uint32_t)s.constraints.size();
     if (s.world) { edynhip_world_destroy(s.world); s.world = nullptr; }
@@ -729,6 +734,54 @@ inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     for (const auto &e : s.exclusions) check(s, edynhip_world_exclude_collision(s.world, e[0], e[1]));
     s.uploaded_bodies = total; s.uploaded_constraints = nj; s.exclusions_uploaded = s.exclusions.size();
     s.scene_dirty = false; s.state_dirty = false;
+    s.recreate = false; s.refresh_friction = false; s.reshaped.clear();   // (the new world was described with the current components)
+    s.params_dirty = false;                                               // (... and created with the current settings)
+}
+// upload_scene's append path on a multi-device world: bodies, constraints, definitions and exclusions made since the last upload go to
+// the running world (edynhip_world_add_bodies / _add_joints / _edit_joint / _edit_exclusion); nothing is rebuilt.
+inline void append_scene_multi(entt::registry &registry, gpu_stepper &s) {
+    const uint32_t total = (uint32_t)s.bodies.size(), nj = (uint32_t)s.constraints.size();
+    const uint32_t first = s.uploaded_bodies, n = total - first;
+    for (uint32_t i = first; i < total; ++i) {   // a convex mesh created after the bodies: a fresh upload, as on one device
+        const entt::entity e = s.bodies[i];
+        const polyhedron_shape *ph = e != entt::null ? registry.try_get<polyhedron_shape>(e) : nullptr;
+        bool known = ph == nullptr;
+        if (ph) for (auto &m : s.meshes) known = known || m.first == ph->mesh;
+        if (!known) { upload_scene_multi(registry, s); return; }
+    }
+    if (n) {
+        body_arrays A(n);
+        fill_body_arrays(registry, s, first, n, A, [&](const polyhedron_shape &ph) {
+            uint32_t id = ~0u;
+            for (auto &known : s.meshes) if (known.first == ph.mesh) id = known.second;
+            return id;
+        });
+        if (A.any_extras || A.any_ids) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: contact_extras materials and material ids are single-device features (init_config::devices)");
+        const edynhip_bodies b = A.view();
+        uint32_t first_index = 0;
+        check(s, edynhip_world_add_bodies(s.world, n, &b, &first_index));
+        if (!A.dead.empty()) check(s, edynhip_world_remove_bodies(s.world, (uint32_t)A.dead.size(), A.dead.data()));
+        s.uploaded_bodies = total;
+    }
+    if (nj > s.uploaded_constraints) {
+        std::vector<int32_t> jt; std::vector<uint32_t> jb; std::vector<float> jp, ja, jq;
+        std::vector<uint32_t> dead_joints;
+        joint_arrays(registry, s, s.uploaded_constraints, jt, jb, jp, ja, jq, dead_joints);
+        uint32_t anybody = 0;   // a constraint destroyed before it went up keeps its index: a rowless self-edge on a living body, removed below
+        for (uint32_t i = 0; i < total; ++i) if (s.bodies[i] != entt::null) { anybody = i; break; }
+        for (uint32_t j : dead_joints) { const uint32_t k = j - s.uploaded_constraints; jt[k] = EDYNHIP_JOINT_NULL; jb[2 * k] = jb[2 * k + 1] = anybody; }
+        edynhip_joints js{jt.data(), jb.data(), jp.data(), ja.data(), jq.data()};
+        uint32_t first_joint = 0;
+        check(s, edynhip_world_add_joints(s.world, nj - s.uploaded_constraints, &js, &first_joint));
+        upload_joint_defs(registry, s, s.uploaded_constraints, nj, [&](uint32_t j, const float *fa, const float *fb, const float *q, bool generic) {
+            check(s, edynhip_world_edit_joint(s.world, j, fa, fb, q, generic ? 1 : 0));
+        });
+        if (!dead_joints.empty()) check(s, edynhip_world_remove_joints(s.world, (uint32_t)dead_joints.size(), dead_joints.data()));
+        s.uploaded_constraints = nj;
+    }
+    for (size_t k = s.exclusions_uploaded; k < s.exclusions.size(); ++k) check(s, edynhip_world_edit_exclusion(s.world, s.exclusions[k][0], s.exclusions[k][1], 1));
+    s.exclusions_uploaded = s.exclusions.size();
+    s.scene_dirty = false;
 }
 
 constexpr uint32_t prefetch_events_max = 8192;   // contact events that travel ahead of a step's state (sequential modes); more = read after the step
@@ -904,7 +957,7 @@ inline void upload_state(entt::registry &registry, gpu_stepper &s) {
         if (auto *v = registry.try_get<linvel>(e)) { lv[3 * i] = v->x; lv[3 * i + 1] = v->y; lv[3 * i + 2] = v->z; }
         if (auto *w = registry.try_get<angvel>(e)) { av[3 * i] = w->x; av[3 * i + 1] = w->y; av[3 * i + 2] = w->z; }
     }
-    check(s, edynhip_set_state(s.ctx, pos.data(), orn.data(), lv.data(), av.data()));
+    check(s, s.world ? edynhip_world_set_state(s.world, pos.data(), orn.data(), lv.data(), av.data()) : edynhip_set_state(s.ctx, pos.data(), orn.data(), lv.data(), av.data()));
     s.state_dirty = false;
 }
 
@@ -1034,18 +1087,23 @@ inline void sync_removed(entt::registry &registry, gpu_stepper &s) {
             if (j < s.uploaded_constraints) gone_joints.push_back(j);
         }
     }
+    if (s.world) {   // init_config::devices: the same two edits on the running multi-device world
+        if (!gone_joints.empty()) check(s, edynhip_world_remove_joints(s.world, (uint32_t)gone_joints.size(), gone_joints.data()));
+        if (!gone_bodies.empty()) check(s, edynhip_world_remove_bodies(s.world, (uint32_t)gone_bodies.size(), gone_bodies.data()));
+        return;
+    }
     if (!s.ctx) return;
     if (!gone_joints.empty()) check(s, edynhip_remove_joints(s.ctx, (uint32_t)gone_joints.size(), gone_joints.data()));
     if (!gone_bodies.empty()) check(s, edynhip_remove_bodies(s.ctx, (uint32_t)gone_bodies.size(), gone_bodies.data()));
 }
-inline void apply_params(gpu_stepper &s) {   // settings on the running context: nothing is re-created, no contact state is lost
-    if (!s.ctx || !s.params_dirty) { s.params_dirty = false; return; }
+inline void apply_params(gpu_stepper &s) {   // settings on the running context (or multi-device world): nothing is re-created, no contact state is lost
+    if ((!s.ctx && !s.world) || !s.params_dirty) { s.params_dirty = false; return; }
     edynhip_params p{};
     p.fixed_dt = s.cfg.fixed_dt;
     p.num_velocity_iterations = s.cfg.num_solver_velocity_iterations;
     p.num_position_iterations = s.cfg.num_solver_position_iterations;
     p.gravity[0] = s.cfg.gravity.x; p.gravity[1] = s.cfg.gravity.y; p.gravity[2] = s.cfg.gravity.z;
-    check(s, edynhip_set_params(s.ctx, &p));
+    check(s, s.world ? edynhip_world_set_params(s.world, &p) : edynhip_set_params(s.ctx, &p));
     s.params_dirty = false;
 }
 // Contact entities. The device reports what changed (edynhip_get_contact_events); the registry follows: a
@@ -1234,13 +1292,13 @@ inline void run_steps(entt::registry &registry, gpu_stepper &s, unsigned steps, 
     if (s.multi()) {   // init_config::devices: the multi-GPU world (see upload_scene_multi)
         if (async || s.pre_step || s.post_step || s.cfg.contact_point_data)
             throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: asynchronous mode, step callbacks and contact entities are single-device features (init_config::devices)");
-        const size_t gone_before = (size_t)std::count(s.bodies.begin(), s.bodies.end(), entt::entity{entt::null}) + (size_t)std::count(s.constraints.begin(), s.constraints.end(), entt::entity{entt::null});
+        // the single-device sequence on the running world: removals, what was made since the last upload, the edited state, the settings
         sync_removed(registry, s);
-        const size_t gone_after = (size_t)std::count(s.bodies.begin(), s.bodies.end(), entt::entity{entt::null}) + (size_t)std::count(s.constraints.begin(), s.constraints.end(), entt::entity{entt::null});
-        if (gone_after != gone_before || s.params_dirty) s.scene_dirty = true;   // settings travel with the world's creation
-        s.params_dirty = false;
         if (s.bodies.empty()) return;
-        if (s.scene_dirty || s.state_dirty || !s.world) upload_scene_multi(registry, s);
+        if (!s.world || s.recreate) upload_scene_multi(registry, s);
+        else if (s.scene_dirty) append_scene_multi(registry, s);
+        if (s.state_dirty) upload_state(registry, s);
+        apply_params(s);
         if (steps == 0) return;
         check(s, edynhip_world_step(s.world, steps));
         const uint32_t n = (uint32_t)s.bodies.size();
@@ -1745,6 +1803,7 @@ inline void remove_collision_exclusion(entt::registry &registry, entt::entity fi
         }
     }
     if (on_device && s.ctx && a < s.uploaded_bodies && b < s.uploaded_bodies) detail::check(s, edynhip_remove_collision_exclusion(s.ctx, a, b));
+    if (on_device && s.world && a < s.uploaded_bodies && b < s.uploaded_bodies) detail::check(s, edynhip_world_edit_exclusion(s.world, a, b, 0));
 }
 /// util/exclude_collision.hpp:23 (entity_pair form) and :38 clear_collision_exclusion (exclude_collision.cpp:59-69): every exclusion `entity` takes part in
 using entity_pair = std::pair<entt::entity, entt::entity>;   // core/entity_pair.hpp

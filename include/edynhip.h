@@ -669,6 +669,57 @@ int edynhip_world_query_aabb_device(edynhip_world *w, int category, uint32_t n, 
  * A shard context (edynhip_world_context) stays read-only: its own edynhip_get_contact_events speaks local indices. */
 int edynhip_world_get_contact_events(edynhip_world *w, edynhip_contact_event *out, uint32_t capacity, uint32_t *n);
 int edynhip_world_get_point_ids(edynhip_world *w, uint64_t *ids, uint32_t capacity_manifolds, uint32_t *n);
+/* Edits of a RUNNING multi-device world (additive to ABI 15): what edynhip_add_bodies / _remove_bodies / _add_joints / _remove_joints /
+ * _set_joint_params / _set_joint_definition / _set_generic_definition / _exclude_collision / _remove_collision_exclusion / _set_state /
+ * _get_params / _set_params do on one context, in GLOBAL indices - registry.create + make_rigidbody and registry.destroy on a running
+ * world (src/edyn/util/rigidbody.cpp:18-161, src/edyn/edyn.cpp:148-197, island_manager.cpp:47-115), make_constraint / destroy of a
+ * constraint (include/edyn/util/constraint_util.hpp:38-54, island_manager.cpp:68-97), registry.patch of a constraint, exclude_collision
+ * (src/edyn/util/exclude_collision.cpp:9-71), edyn::refresh of the state pools, set_fixed_dt / set_solver_*_iterations / set_gravity
+ * (src/edyn/edyn.cpp:203-207). After any sequence of these and steps the world returns, bit for bit, what ONE context holding the whole
+ * scene returns after the same edits and steps.
+ *   indices   new bodies take num_bodies .., new joints the next joint indices (*first_index, may be NULL); a removed body's index stays
+ *             reserved (the slot is a shapeless static body, edynhip_world_get_partition reports -1 for it), its joints go with it and the
+ *             islands it touched wake up; a removed joint keeps its index. Removing what is already removed is accepted and does nothing.
+ *   placement a new body that is not dynamic is replicated on every shard (shard 0 reports it); a new dynamic body goes to the shard that
+ *             owns the fewest live dynamic bodies at that moment (the bodies of one call are placed one after the other in index order;
+ *             ties: the lowest shard) and takes with it every later body of the same call that it touches, directly or through others
+ *             (the boxes of their bounding spheres within the manifold-creation margin): a pile spawned in one call lands on one shard.
+ *   safety    before the next step no body of one shard is within the manifold-creation margin of an island of another and no joint spans
+ *             two shards: after a shaped dynamic body was added the world runs its approach check (new bodies are islands of their own)
+ *             and, if that says "close", the sticky re-partition; a joint between two shards re-partitions first (its islands move
+ *             together by the sticky rule) and is then made in place; edynhip_world_set_state makes the check due after the next step,
+ *             which is when a context's broadphase first sees the moved boxes.
+ *   in place  every edit is forwarded to the shard context(s) that hold the bodies / the joint and the world's tables follow: no shard is
+ *             rebuilt and nothing is re-partitioned unless the safety rule asks for it. An add that exceeds a shard's body or joint
+ *             capacity first rebuilds THAT shard with head-room through what a re-partition carries (manifolds with impulses and point
+ *             ids, joint impulses and angles, sleep state) and then runs in place; edynhip_world_edit_stats counts each path.
+ *   described On a world that is described but whose shards are not built yet the calls extend or alter the description.
+ *   errors    out-of-range indices, missing arrays, a joint to a removed body: EDYNHIP_ERR_INVALID (edynhip_world_last_error); the world
+ *             is left as it was.
+ * The three scene-description calls above keep refusing a stepped world and edynhip_world_set_bodies still starts a new world.
+ * edynhip_world_edit_joint: generic = -1: params[10] (edynhip_set_joint_params; frames ignored, may be NULL), 0: params[16]
+ * (edynhip_set_joint_definition), 1: params[60] (edynhip_set_generic_definition). edynhip_world_edit_exclusion: exclude = 1
+ * edynhip_exclude_collision, 0 edynhip_remove_collision_exclusion. */
+typedef struct {
+    uint32_t edits;                   /* edit calls that changed a built world */
+    uint32_t in_place;                /* ... of which ran without rebuilding a shard and without a re-partition */
+    uint32_t shard_rebuilds;          /* shards rebuilt with head-room because an add did not fit */
+    uint32_t repartitions_by_edit;    /* sticky re-partitions an edit caused (close islands, a joint between two shards) */
+    uint32_t approach_checks_by_edit; /* approach checks run right after an edit */
+} edynhip_world_edit_stats;
+int edynhip_world_add_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies *bodies, uint32_t *first_index);
+int edynhip_world_remove_bodies(edynhip_world *w, uint32_t n, const uint32_t *body_indices);
+int edynhip_world_add_joints(edynhip_world *w, uint32_t n, const edynhip_joints *joints, uint32_t *first_index);
+int edynhip_world_remove_joints(edynhip_world *w, uint32_t n, const uint32_t *joint_indices);
+int edynhip_world_edit_joint(edynhip_world *w, uint32_t joint, const float *frame_a9, const float *frame_b9, const float *params, int generic);
+int edynhip_world_edit_exclusion(edynhip_world *w, uint32_t body_a, uint32_t body_b, int exclude);
+int edynhip_world_set_state(edynhip_world *w, const float *pos, const float *orn, const float *linvel, const float *angvel);
+int edynhip_world_get_params(edynhip_world *w, edynhip_params *out);
+int edynhip_world_set_params(edynhip_world *w, const edynhip_params *params);
+int edynhip_world_get_edit_stats(edynhip_world *w, edynhip_world_edit_stats *out);
+/* edynhip_get_asleep on the whole world (additive to ABI 15): asleep[num_bodies], every body's sleeping_tag from the shard that reports
+ * its state; all 0 without EDYNHIP_FLAG_SLEEPING. (With tombstones in the world the partition no longer tells which bodies a shard holds.) */
+int edynhip_world_get_asleep(edynhip_world *w, uint8_t *asleep);
 /* edynhip_debug_paths of a multi-device world (additive to ABI 15): the OR over every shard context the world has had, plus
  * EDYNHIP_PATH_WORLD_SERIAL when the shards were stepped one after the other on the caller's thread. */
 int edynhip_world_debug_paths(edynhip_world *w, uint64_t *mask);
