@@ -50,7 +50,7 @@ class Timings(C.Structure):
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("num_bodies", "num_manifolds", "num_points", "num_active_manifolds",
                                           "num_islands", "num_colours", "num_joint_colours", "colour_rounds",
-                                          "num_joints", "num_joint_rows", "solve_schedule")] + [("colour_size", C.c_uint32 * 64)]
+                                          "num_joints", "num_joint_rows", "solve_schedule")] + [("colour_size", C.c_uint32 * 64), ("lean_rows", C.c_uint32)]
 
 
 class WorldStats(C.Structure):   # edynhip_world_stats
@@ -79,6 +79,7 @@ MANIFOLD_DTYPE = np.dtype([
 
 FLAG_TIMING, FLAG_SLEEPING, FLAG_EXCLUSIVE_DEVICE, FLAG_TIMING_SOLVE, FLAG_CONTACT_EVENTS = 1, 4, 8, 16, 32
 FLAG_FUSED_VELOCITY_ROWS, FLAG_BLOCK_POSITION = 64, 128   # opt-in contact arithmetic (edynhip.h); default: the reference's operations
+FLAG_FULL_CONTACT_ROWS = 256   # A/B and test aid: no lean contact rows (edynhip.h)
 PAIR_FILTER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32)   # edynhip_pair_filter: int filter(void *user, uint32_t body, uint32_t other)
 EVENT_DTYPE = np.dtype([("type", np.uint32), ("step", np.uint32), ("body", np.uint32, 2), ("point_id", np.uint64)])
 EVENT_MANIFOLD_CREATED, EVENT_MANIFOLD_DESTROYED, EVENT_POINT_CREATED, EVENT_POINT_DESTROYED = 1, 2, 3, 4

@@ -174,7 +174,12 @@ struct HostJoint {
 // its solve loop, so results stay bit-identical.
 // Row r of point slot k of lane p lives at rw[((k*3 + r)*5 + f) * cap + p], r = 0 normal, 1/2 friction tangents:
 //   f=0: J_lin.xyz (n or t; J[2] = -J_lin), eff_mass     f=1: J_angA.xyz, rhs      f=2: J_angB.xyz, impulse
-//   f=3: inv_IA * J_angA .xyz, mu (normal row only)      f=4: inv_IB * J_angB .xyz
+//   f=3: inv_IA * J_angA .xyz, mu (normal row only)      f=4: inv_IB * J_angB .xyz, upper limit (normal row only)
+// Lean rows (solver.hip SolvePlan::lean: a contact-only world whose velocity solve is one dataflow launch): planes 3 and 4 are neither
+// written nor read - 48 instead of 80 bytes per row. The dataflow kernels rebuild both products before they wait for their hand-offs, with
+// the mul() that k_prep_contacts would have stored them with (the same bits), from a lane-indexed copy of the two bodies' world inverse
+// inertias, Rows::iw, whose spare .w lanes carry the points' friction coefficients; the upper limit is kLarge on that path. The
+// addressing of rw does not change (kRowF stays 5), and every other schedule keeps full rows.
 struct Rows {
     uint32_t *order = nullptr;    // p -> manifold index
     uint32_t *bA = nullptr, *bB = nullptr, *np = nullptr;
@@ -195,6 +200,8 @@ struct Rows {
     uint32_t *slot_of = nullptr;  // [body * 64 + colour] -> slot, scratch for building `next`
     uint32_t *first_slot = nullptr;   // per body: slot of its lowest-colour manifold (where a sweep leaves its deltas), or ~0
     uint8_t *skip = nullptr;          // [p] mixed schedule: the manifold's island has joints (solved by the island-fused kernels, not on the chains)
+    float4 *iw = nullptr;             // lean rows only, [(3 * side + j) * cap + p]: row j of that side's world inverse inertia as load_bref gives it
+                                      // (zeros for a read-only body); .w of plane k (k < 4) = friction coefficient of point k
 };
 constexpr int kRowF = 5, kRowsPerPoint = 3, kPosF = 4;
 constexpr uint32_t kColUncCap = 16384;   // uncoloured edges one workgroup colours by itself (more: the multi-block rounds)

@@ -59,17 +59,22 @@ __global__ void k_solve_begin(uint32_t n, Bodies b, float dt, uint32_t *first_sl
     if (i < n) solve_begin_body(i, b, dt, first_slot);
 }
 
+// LEAN (lean rows, ctx.hpp Rows::iw): planes 3 and 4 are not written - the dataflow kernels rebuild them with the same mul().
+template <bool LEAN>
 DI void store_row(float4 *rw, size_t base, size_t cap, f3 Jl, f3 JaA, f3 JaB, float eff, float rhs, float imp, float mu,
                   const BRef &A, const BRef &B) {
     rw[base] = to4(Jl, eff);
     rw[base + cap] = to4(JaA, rhs);
     rw[base + 2 * cap] = to4(JaB, imp);
+    if (LEAN) return;
     rw[base + 3 * cap] = to4(mul(A.inv_I, JaA), mu);
     rw[base + 4 * cap] = to4(mul(B.inv_I, JaB), kLarge);   // .w of a normal row: its upper limit (soft contacts lower it)
 }
 // EXTRAS: the world has contact_extras materials (soft normal rows, rolling / spinning rows); the plain instantiation is the
 // headline path and carries none of that code.
-template <bool EXTRAS>
+// LEAN (never with EXTRAS): lean rows for the dataflow velocity kernels of a contact-only world (SolvePlan::lean) - a row keeps planes 0-2,
+// and the manifold's lane gets both bodies' world inverse inertia, with the points' friction coefficients in the .w lanes (Rows::iw).
+template <bool EXTRAS, bool LEAN>
 __global__ void k_prep_contacts(uint32_t n_active, Rows rows, uint32_t rcap, Manifolds mf, Bodies b, float dt,
                                 const uint32_t *__restrict__ keys_sorted, bool push, bool by_key, bool write_pw) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -90,6 +95,14 @@ __global__ void k_prep_contacts(uint32_t n_active, Rows rows, uint32_t rcap, Man
     // (One lane per contact POINT instead of per manifold was measured - the points of a manifold are independent here - and is slower,
     //  103 against 71 us on the headline pile: every lane then loads both bodies for a single point.)
     const BRef A = load_bref(b, ia), B = load_bref(b, ib);
+    if (LEAN) {   // plane 3 * side + j = row j of that side's inverse inertia as load_bref gave it (zeros for a read-only body); .w of plane k = mu of point k
+        float mus[kMaxPts];
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)kMaxPts; ++k) mus[k] = k < np ? mf.pB[pt_at(mf.cap, k, m)].w : 0.0f;
+        float4 *iw = rows.iw + p;
+        iw[0] = to4(A.inv_I.r0, mus[0]); iw[rcap] = to4(A.inv_I.r1, mus[1]); iw[2 * (size_t)rcap] = to4(A.inv_I.r2, mus[2]);
+        iw[3 * (size_t)rcap] = to4(B.inv_I.r0, mus[3]); iw[4 * (size_t)rcap] = to4(B.inv_I.r1, 0.0f); iw[5 * (size_t)rcap] = to4(B.inv_I.r2, 0.0f);
+    }
     for (uint32_t k = 0; k < np; ++k) {
         const size_t s = slot_at(mf.cap, k, m), t = pt_at(mf.cap, k, m);   // (s: the slot-major extras arrays; t: the manifold's point record)
         const float4 a4 = mf.pA[t], b4 = mf.pB[t], n4 = mf.nrm[t], im = mf.imp[t];
@@ -124,7 +137,7 @@ __global__ void k_prep_contacts(uint32_t n_active, Rows rows, uint32_t rcap, Man
         const float rhs0 = -rel_speed(t0, K1, -t0, K3, A.v, A.w, B.v, B.w);
         const float rhs1 = -rel_speed(t1, L1, -t1, L3, A.v, A.w, B.v, B.w);
         const size_t base = (size_t)(k * kRowsPerPoint) * kRowF * rcap + p, rstride = (size_t)kRowF * rcap;
-        store_row(rows.rw, base, rcap, n, J1, J3, effn, rhsn, im.x, mu, A, B);
+        store_row<LEAN>(rows.rw, base, rcap, n, J1, J3, effn, rhsn, im.x, mu, A, B);
         if (!EXTRAS && push && write_pw) {   // the dataflow position solve's copy of the point, indexed by the lane (Rows::pw)
             const size_t pb = (size_t)(k * kPosF) * rcap + p;
             rows.pw[pb] = a4; rows.pw[pb + rcap] = b4; rows.pw[pb + 2 * (size_t)rcap] = mf.lnrm[t]; rows.pw[pb + 3 * (size_t)rcap] = n4;
@@ -160,8 +173,8 @@ __global__ void k_prep_contacts(uint32_t n_active, Rows rows, uint32_t rcap, Man
             }
             if (xm.y > 0) axial(2, n, xi.z, false);
         }
-        store_row(rows.rw, base + rstride, rcap, t0, K1, K3, eff0, rhs0, im.y, 0.0f, A, B);
-        store_row(rows.rw, base + 2 * rstride, rcap, t1, L1, L3, eff1, rhs1, im.z, 0.0f, A, B);
+        store_row<LEAN>(rows.rw, base + rstride, rcap, t0, K1, K3, eff0, rhs0, im.y, 0.0f, A, B);
+        store_row<LEAN>(rows.rw, base + 2 * rstride, rcap, t1, L1, L3, eff1, rhs1, im.z, 0.0f, A, B);
     }
 }
 
@@ -526,6 +539,7 @@ struct DfArgs {
     const uint8_t *skip;              // mixed schedule: [p] != 0 = the manifold's island has joints and is solved by k_island_velocity; else nullptr
     uint32_t nap;                     // pause between two polls of a wave that found nothing: 0 none, 1 s_sleep 1, else s_sleep 4 (EDYNHIP_DF_NAP, developer knob)
     uint32_t xcd_lists;               // two-lane kernel: tasks are handed out per XCD (XcdLists below) instead of by p alone
+    const float4 *iw;                 // Rows::iw (the LEAN kernels; unused by the others)
 };
 // ---- XCD-local task lists (round 5) ---------------------------------------------------------------------------------------------------
 // A hand-off between two waves of the SAME XCD is noticed ~0.2 us sooner than one that crosses XCDs (scripts/ubench/pingpong.hip: 280 against
@@ -599,7 +613,17 @@ constexpr uint32_t kDfSpinLimit = 1u << 22;   // ~seconds; a hand-off normally a
 //  741.9 against 751.5; the default pile, four lanes and chains16k stayed level. With the one-lane kernel back in the parent's form and the
 //  two-lane kernel back on the parent's task loop, the rest still shared: mixed32k 716.3 against 722.9, fused arithmetic 894.5 against
 //  909.7. So the four copies stay, and a fix in one of them still has to be made in all four.)
-template <bool WARM, int NP, bool FUSED>
+// LEAN (lean rows, Rows::iw): a row's planes 3 and 4 are not loaded but rebuilt from its J_ang and the lane's copy of the two inverse
+// inertias - store_row's own mul(), hence the stored bits - and the friction coefficients come from that copy's .w lanes.
+template <bool LEAN>
+DI void row_load_df(RowReg &r, const float4 *__restrict__ rw, uint32_t rcap, uint32_t p, int k, int row, const m3 &iA, const m3 &iB) {
+    if (!LEAN) { row_load(r, rw, rcap, p, k, row); return; }
+#pragma unroll
+    for (int f = 0; f < 3; ++f) r.f[f] = rw[(size_t)((k * kRowsPerPoint + row) * kRowF + f) * rcap + p];
+    r.f[3] = to4(mul(iA, from4(r.f[1])), 0.0f);
+    r.f[4] = to4(mul(iB, from4(r.f[2])), 0.0f);
+}
+template <bool WARM, int NP, bool FUSED, bool LEAN>
 DI void df_task(const DfArgs &a, uint32_t p, bool valid, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *trace_slot) {
     // Rows fetched before the wait: every normal row and the friction rows of the first two points. The friction rows
     // of points 2 and 3 are fetched when the hand-offs have arrived and land while the normal rows are being solved;
@@ -607,10 +631,24 @@ DI void df_task(const DfArgs &a, uint32_t p, bool valid, uint32_t np, uint32_t c
     constexpr int kEarly = NP > 2 ? 2 : NP;
     RowReg Rn[NP], Rf[NP][2];
     const uint64_t w0 = a.trace ? wall_clock64() : 0;
+    m3 iA = m3_zero(), iB = m3_zero();
+    float mu[NP];
+    if (LEAN) {
+        float4 i4[6];
 #pragma unroll
-    for (int k = 0; k < NP; ++k) row_load(Rn[k], a.rw, a.rcap, p, k, 0);
+        for (int f = 0; f < 6; ++f) i4[f] = a.iw[(size_t)f * a.rcap + p];
+        iA = {from4(i4[0]), from4(i4[1]), from4(i4[2])}; iB = {from4(i4[3]), from4(i4[4]), from4(i4[5])};
 #pragma unroll
-    for (int k = 0; k < kEarly; ++k) { row_load(Rf[k][0], a.rw, a.rcap, p, k, 1); row_load(Rf[k][1], a.rw, a.rcap, p, k, 2); }
+        for (int k = 0; k < NP; ++k) mu[k] = i4[k].w;
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) row_load_df<LEAN>(Rn[k], a.rw, a.rcap, p, k, 0, iA, iB);
+#pragma unroll
+    for (int k = 0; k < kEarly; ++k) { row_load_df<LEAN>(Rf[k][0], a.rw, a.rcap, p, k, 1, iA, iB); row_load_df<LEAN>(Rf[k][1], a.rw, a.rcap, p, k, 2, iA, iB); }
+    if (!LEAN) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) mu[k] = Rn[k].f[3].w;
+    }
     uint64_t w1 = 0, w2 = 0;
     const uint32_t nA = a.next[2 * (size_t)p], nB = a.next[2 * (size_t)p + 1];
     Delta d;
@@ -643,11 +681,11 @@ DI void df_task(const DfArgs &a, uint32_t p, bool valid, uint32_t np, uint32_t c
             if (a.trace && w2 == 0) w2 = wall_clock64();
             if (mine_now) {
 #pragma unroll
-                for (int k = kEarly; k < NP; ++k) { row_load(Rf[k][0], a.rw, a.rcap, p, k, 1); row_load(Rf[k][1], a.rw, a.rcap, p, k, 2); }
+                for (int k = kEarly; k < NP; ++k) { row_load_df<LEAN>(Rf[k][0], a.rw, a.rcap, p, k, 1, iA, iB); row_load_df<LEAN>(Rf[k][1], a.rw, a.rcap, p, k, 2, iA, iB); }
                 rows_solve_normals<WARM, NP, FUSED>(d, Rn, np);
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
-                    if ((uint32_t)k < np) solve_friction_pair<Lanes1, WARM, FUSED>(d, Rf[k][0], Rf[k][1], Rn[k].f[3].w, Rn[k].f[2].w);
+                    if ((uint32_t)k < np) solve_friction_pair<Lanes1, WARM, FUSED>(d, Rf[k][0], Rf[k][1], mu[k], Rn[k].f[2].w);
                 // hand the deltas over first (the next manifolds are waiting for them), then store the impulses
                 if (d.imA != 0) df_publish(a.dslot + dslot_at(nA & kSlotMask, 0), d.dvA, d.dwA, sweep + 1);
                 if (d.imB != 0) df_publish(a.dslot + dslot_at(nB & kSlotMask, 0), d.dvB, d.dwB, sweep + 1);
@@ -672,7 +710,7 @@ DI void df_task(const DfArgs &a, uint32_t p, bool valid, uint32_t np, uint32_t c
     }
 }
 constexpr uint32_t kDfBlock = 64;   // one wave per workgroup: the dispatcher spreads the waves over all CUs
-template <bool FUSED>
+template <bool FUSED, bool LEAN>
 __global__ void __launch_bounds__(kDfBlock) k_contact_solve_df(DfArgs a) {
     const uint32_t t = blockIdx.x * 64u + threadIdx.x;
     const uint32_t rounds = (a.na + a.stride - 1) / a.stride, nwaves = a.stride >> 6;
@@ -686,8 +724,8 @@ __global__ void __launch_bounds__(kDfBlock) k_contact_solve_df(DfArgs a) {
             const uint32_t np = 4u - (key & 3u), col = key >> 2;
             const bool big = __any(valid && np > 2);  // lanes are grouped by point count: uniform except at a group boundary
             uint64_t *tr = a.trace ? a.trace + 4 * ((size_t)(sweep * rounds + round) * nwaves + blockIdx.x) : nullptr;
-            if (sweep == 0) { if (big) df_task<true, 4, FUSED>(a, p, valid, np, col, sweep, tr); else df_task<true, 2, FUSED>(a, p, valid, np, col, sweep, tr); }
-            else { if (big) df_task<false, 4, FUSED>(a, p, valid, np, col, sweep, tr); else df_task<false, 2, FUSED>(a, p, valid, np, col, sweep, tr); }
+            if (sweep == 0) { if (big) df_task<true, 4, FUSED, LEAN>(a, p, valid, np, col, sweep, tr); else df_task<true, 2, FUSED, LEAN>(a, p, valid, np, col, sweep, tr); }
+            else { if (big) df_task<false, 4, FUSED, LEAN>(a, p, valid, np, col, sweep, tr); else df_task<false, 2, FUSED, LEAN>(a, p, valid, np, col, sweep, tr); }
         }
 }
 
@@ -1555,7 +1593,9 @@ struct Lanes2 {   // two lanes per manifold: each holds its own body's deltas an
 };
 // EXACT: every live lane of the wave has exactly NP points (the common case: lanes are grouped by point count), so the
 // rows need no per-lane point-count predicate.
-template <bool WARM, int NP, bool EXACT, bool FUSED>
+// LEAN: as in df_task - a lane loads its own side's three inertia planes instead of one I^-1 J_ang plane per row (27 instead of 36 loads
+// for four points); point k's mu is .w of plane k: the A lane's for k < 3, the B lane's first for k = 3.
+template <bool WARM, int NP, bool EXACT, bool FUSED, bool LEAN>
 DI void df2_task(const DfArgs &a, uint32_t p, bool valid, bool sideB, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *trace_slot) {
     Row2 R[NP][kRowsPerPoint];
     float mu[NP];
@@ -1563,6 +1603,12 @@ DI void df2_task(const DfArgs &a, uint32_t p, bool valid, bool sideB, uint32_t n
     const uint32_t slot = 2 * p + (sideB ? 1u : 0u);
     const uint32_t nx = a.next[slot];
     const float im = a.im[slot];
+    float4 i4[3] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
+    if (LEAN) {
+#pragma unroll
+        for (int f = 0; f < 3; ++f) i4[f] = a.iw[(size_t)((sideB ? 3 : 0) + f) * a.rcap + p];
+    }
+    const m3 iw = {from4(i4[0]), from4(i4[1]), from4(i4[2])};   // (LEAN only)
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
 #pragma unroll
@@ -1570,15 +1616,18 @@ DI void df2_task(const DfArgs &a, uint32_t p, bool valid, bool sideB, uint32_t n
             const size_t base = (size_t)((k * kRowsPerPoint + r) * kRowF) * a.rcap + p;
             const float4 f0 = a.rw[base];                                           // (J_lin, eff)
             const float4 fa = a.rw[base + (size_t)(sideB ? 2 : 1) * a.rcap];        // A: (J_angA, rhs)   B: (J_angB, impulse)
-            const float4 fi = a.rw[base + (size_t)(sideB ? 4 : 3) * a.rcap];        // A: (I_A^-1 J_angA, mu)   B: (I_B^-1 J_angB, -)
+            const float4 fi = LEAN ? f0 : a.rw[base + (size_t)(sideB ? 4 : 3) * a.rcap];   // A: (I_A^-1 J_angA, mu)   B: (I_B^-1 J_angB, -)   (not LEAN)
             Row2 &q = R[k][r];
             const f3 Jl = from4(f0);
             q.jl = sideB ? -Jl : Jl;
             q.ijl = im * q.jl;
-            q.ja = from4(fa); q.ija = from4(fi);
+            q.ja = from4(fa); q.ija = LEAN ? mul(iw, q.ja) : from4(fi);
+            // (LEAN, measured and dropped: pinning each row's products as soon as they exist (an empty asm with "+v" operands) keeps the kernel at
+            //  the full-row form's 42 AGPRs instead of 56, but serialises the work before the wait: velocity solve 0.572 against 0.530 ms on
+            //  the headline pile, slower than full rows at 0.557 - profiles/lean_rows_bench_ab.json.)
             q.eff = f0.w;
             q.rhs = FUSED ? dppA(fa.w) * f0.w : dppA(fa.w); q.imp = dppB(fa.w);
-            if (r == 0) mu[k] = dppA(fi.w);
+            if (r == 0) mu[k] = !LEAN ? dppA(fi.w) : k < 3 ? dppA(i4[k < 3 ? k : 0].w) : dppB(i4[0].w);
         }
     }
     Side x;
@@ -1636,19 +1685,19 @@ DI void df2_task(const DfArgs &a, uint32_t p, bool valid, bool sideB, uint32_t n
         }
     }
 }
-template <bool WARM, bool FUSED>
+template <bool WARM, bool FUSED, bool LEAN>
 DI void df2_dispatch(const DfArgs &a, uint32_t p, bool valid, bool sideB, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *tr) {
     // lanes are grouped by point count: np is uniform over a wave except at a group boundary. The warm-start sweep runs
     // once and keeps the predicated form only (fewer instantiations: the kernel has to stay within the instruction cache).
     // Waves of one-point manifolds (sphere contacts: the majority of a mixed scene) get their own instantiation: the NP = 2 form
     // fetched a second point slot in vain for each of them (round 3: 1.30x the algorithmic traffic on mixed32k) and ran its code.
-    if (!WARM && __all(!valid || np == 4u)) df2_task<WARM, 4, true, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
-    else if (!WARM && __all(!valid || np == 2u)) df2_task<WARM, 2, true, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
-    else if (!WARM && __all(!valid || np == 1u)) df2_task<WARM, 1, true, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
-    else if (__any(np > 2u)) df2_task<WARM, 4, false, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
-    else df2_task<WARM, 2, false, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
+    if (!WARM && __all(!valid || np == 4u)) df2_task<WARM, 4, true, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
+    else if (!WARM && __all(!valid || np == 2u)) df2_task<WARM, 2, true, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
+    else if (!WARM && __all(!valid || np == 1u)) df2_task<WARM, 1, true, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
+    else if (__any(np > 2u)) df2_task<WARM, 4, false, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
+    else df2_task<WARM, 2, false, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
 }
-template <bool FUSED>
+template <bool FUSED, bool LEAN>
 __global__ void __launch_bounds__(64) k_contact_solve_df2(DfArgs a) {
     const uint32_t t = blockIdx.x * 32u + (threadIdx.x >> 1);   // 32 manifolds per wave, two lanes each
     const bool sideB = threadIdx.x & 1u;
@@ -1665,8 +1714,8 @@ __global__ void __launch_bounds__(64) k_contact_solve_df2(DfArgs a) {
                 const uint32_t p = pt < a.na ? pt : a.na - 1;
                 const uint32_t key = a.keys_sorted[p];
                 const uint32_t np = valid ? 4u - (key & 3u) : 0u, col = key >> 2;
-                if (sweep == 0) df2_dispatch<true, FUSED>(a, p, valid, sideB, np, col, sweep, nullptr);
-                else df2_dispatch<false, FUSED>(a, p, valid, sideB, np, col, sweep, nullptr);
+                if (sweep == 0) df2_dispatch<true, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, nullptr);
+                else df2_dispatch<false, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, nullptr);
             }
         return;
     }
@@ -1680,8 +1729,8 @@ __global__ void __launch_bounds__(64) k_contact_solve_df2(DfArgs a) {
             const uint32_t key = a.keys_sorted[p];
             const uint32_t np = valid ? 4u - (key & 3u) : 0u, col = key >> 2;
             uint64_t *tr = a.trace ? a.trace + 4 * ((size_t)(sweep * rounds + round) * nwaves + blockIdx.x) : nullptr;
-            if (sweep == 0) df2_dispatch<true, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
-            else df2_dispatch<false, FUSED>(a, p, valid, sideB, np, col, sweep, tr);
+            if (sweep == 0) df2_dispatch<true, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
+            else df2_dispatch<false, FUSED, LEAN>(a, p, valid, sideB, np, col, sweep, tr);
         }
 }
 
@@ -1736,7 +1785,8 @@ struct Lanes4 {   // four lanes per manifold: each holds one 3-vector of the del
     template <bool FUSED> static DI float rhs(const Row4 &r) { return r.rhs; }
     static DI float &imp(Row4 &r) { return r.imp; }
 };
-template <bool WARM, int NP, bool EXACT, bool FUSED>
+// LEAN: as in df2_task; the two angular lanes load their side's inertia planes (mu of point k: .w of plane k, role 1's for k < 3, role 3's first for k = 3).
+template <bool WARM, int NP, bool EXACT, bool FUSED, bool LEAN>
 DI void df4_task(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *trace_slot) {
     Row4 R[NP][kRowsPerPoint];
     float mu[NP];
@@ -1747,6 +1797,12 @@ DI void df4_task(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_
     const uint32_t nx = a.next[slot];
     const float im = a.im[slot];
     const size_t off_a = (size_t)(ang ? 1u + side : 0u) * a.rcap, off_i = (size_t)(3u + side) * a.rcap;
+    float4 i4[3] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
+    if (LEAN && ang) {
+#pragma unroll
+        for (int f = 0; f < 3; ++f) i4[f] = a.iw[(size_t)(3u * side + (uint32_t)f) * a.rcap + p];
+    }
+    const m3 iw = {from4(i4[0]), from4(i4[1]), from4(i4[2])};   // (LEAN only)
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
 #pragma unroll
@@ -1754,14 +1810,14 @@ DI void df4_task(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_
             const size_t base = (size_t)((k * kRowsPerPoint + r) * kRowF) * a.rcap + p;
             const float4 fa = a.rw[base + off_a];     // role 0, 2: (J_lin, eff)   1: (J_angA, rhs)   3: (J_angB, impulse)
             float4 fi = fa;
-            if (ang) fi = a.rw[base + off_i];         // role 1: (I_A^-1 J_angA, mu)   3: (I_B^-1 J_angB, -)
+            if (!LEAN && ang) fi = a.rw[base + off_i];   // role 1: (I_A^-1 J_angA, mu)   3: (I_B^-1 J_angB, -)
             Row4 &q = R[k][r];
             const f3 Ja = from4(fa);
             q.j = role == 2u ? -Ja : Ja;              // body B's linear Jacobian is -J_lin
             const f3 lin = im * q.j;
-            q.ij = ang ? from4(fi) : lin;
+            q.ij = ang ? (LEAN ? mul(iw, Ja) : from4(fi)) : lin;
             q.eff = qb0(fa.w); q.rhs = FUSED ? qb1(fa.w) * q.eff : qb1(fa.w); q.imp = qb3(fa.w);   // rhs * eff, as fused_delta takes it
-            if (r == 0) mu[k] = qb1(fi.w);
+            if (r == 0) mu[k] = !LEAN ? qb1(fi.w) : k < 3 ? qb1(i4[k < 3 ? k : 0].w) : qb3(i4[0].w);
         }
     }
     f3 x = mk3(0, 0, 0);
@@ -1816,14 +1872,14 @@ DI void df4_task(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_
         }
     }
 }
-template <bool WARM, bool FUSED>
+template <bool WARM, bool FUSED, bool LEAN>
 DI void df4_dispatch(const DfArgs &a, uint32_t p, bool valid, uint32_t role, uint32_t np, uint32_t col, uint32_t sweep, uint64_t *tr) {
-    if (!WARM && __all(!valid || np == 4u)) df4_task<WARM, 4, true, FUSED>(a, p, valid, role, np, col, sweep, tr);
-    else if (!WARM && __all(!valid || np == 2u)) df4_task<WARM, 2, true, FUSED>(a, p, valid, role, np, col, sweep, tr);
-    else if (__any(np > 2u)) df4_task<WARM, 4, false, FUSED>(a, p, valid, role, np, col, sweep, tr);
-    else df4_task<WARM, 2, false, FUSED>(a, p, valid, role, np, col, sweep, tr);
+    if (!WARM && __all(!valid || np == 4u)) df4_task<WARM, 4, true, FUSED, LEAN>(a, p, valid, role, np, col, sweep, tr);
+    else if (!WARM && __all(!valid || np == 2u)) df4_task<WARM, 2, true, FUSED, LEAN>(a, p, valid, role, np, col, sweep, tr);
+    else if (__any(np > 2u)) df4_task<WARM, 4, false, FUSED, LEAN>(a, p, valid, role, np, col, sweep, tr);
+    else df4_task<WARM, 2, false, FUSED, LEAN>(a, p, valid, role, np, col, sweep, tr);
 }
-template <bool FUSED>
+template <bool FUSED, bool LEAN>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_contact_solve_df4(DfArgs a) {
     const uint32_t t = blockIdx.x * 16u + (threadIdx.x >> 2);   // 16 manifolds per wave, four lanes each
     const uint32_t role = threadIdx.x & 3u;
@@ -1837,8 +1893,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const uint32_t key = a.keys_sorted[p];
             const uint32_t np = valid ? 4u - (key & 3u) : 0u, col = key >> 2;
             uint64_t *tr = a.trace ? a.trace + 4 * ((size_t)(sweep * rounds + round) * nwaves + blockIdx.x) : nullptr;
-            if (sweep == 0) df4_dispatch<true, FUSED>(a, p, valid, role, np, col, sweep, tr);
-            else df4_dispatch<false, FUSED>(a, p, valid, role, np, col, sweep, tr);
+            if (sweep == 0) df4_dispatch<true, FUSED, LEAN>(a, p, valid, role, np, col, sweep, tr);
+            else df4_dispatch<false, FUSED, LEAN>(a, p, valid, role, np, col, sweep, tr);
         }
 }
 template <int NP, bool BLOCK>
@@ -2652,10 +2708,16 @@ static ContactSerialFn contact_serial_fn(bool warm, bool fused) {
     static const ContactSerialFn t[2][2] = {{k_contact_solve_serial<false, false>, k_contact_solve_serial<false, true>}, {k_contact_solve_serial<true, false>, k_contact_solve_serial<true, true>}};
     return t[warm][fused];
 }
-static const void *df_velocity_fn(uint32_t lanes, bool fused) {
-    if (lanes == 4u) return fused ? (const void *)k_contact_solve_df4<true> : (const void *)k_contact_solve_df4<false>;
-    if (lanes == 2u) return fused ? (const void *)k_contact_solve_df2<true> : (const void *)k_contact_solve_df2<false>;
-    return fused ? (const void *)k_contact_solve_df<true> : (const void *)k_contact_solve_df<false>;
+// (the full-row forms are named first, in the order they always were: see the note at prep_contacts on what the order moves)
+static const void *df_velocity_fn(uint32_t lanes, bool fused, bool lean) {
+    if (!lean) {
+        if (lanes == 4u) return fused ? (const void *)k_contact_solve_df4<true, false> : (const void *)k_contact_solve_df4<false, false>;
+        if (lanes == 2u) return fused ? (const void *)k_contact_solve_df2<true, false> : (const void *)k_contact_solve_df2<false, false>;
+        return fused ? (const void *)k_contact_solve_df<true, false> : (const void *)k_contact_solve_df<false, false>;
+    }
+    if (lanes == 4u) return fused ? (const void *)k_contact_solve_df4<true, true> : (const void *)k_contact_solve_df4<false, true>;
+    if (lanes == 2u) return fused ? (const void *)k_contact_solve_df2<true, true> : (const void *)k_contact_solve_df2<false, true>;
+    return fused ? (const void *)k_contact_solve_df<true, true> : (const void *)k_contact_solve_df<false, true>;
 }
 static const void *df_position_fn(bool block) { return block ? (const void *)k_pos_contacts_df<true> : (const void *)k_pos_contacts_df<false>; }
 
@@ -2671,7 +2733,8 @@ static void probe_dataflow(edynhip_ctx *c, bool fused_rows, bool block_pos) {
             int per_cu = 0;
             return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kDfBlock, 0) == hipSuccess && per_cu > 0 ? (uint32_t)per_cu * (uint32_t)ncu : 0u;
         };
-        for (uint32_t lanes : {1u, 2u, 4u}) c->df_resident[lanes] = resident(df_velocity_fn(lanes, fused_rows));
+        // (the full-row and the lean-row form of a kernel hold the same number of waves: the smaller of the two, should they ever differ)
+        for (uint32_t lanes : {1u, 2u, 4u}) c->df_resident[lanes] = std::min(resident(df_velocity_fn(lanes, fused_rows, false)), resident(df_velocity_fn(lanes, fused_rows, true)));
         c->dfp_waves = resident(df_position_fn(block_pos));
         if (c->df_resident[1] > 0) c->df_mode = 1;   // (the one-lane kernel is what the others fall back to)
     }
@@ -2693,11 +2756,12 @@ struct SolvePlan {
     bool mixed = false;             // islands with joints on the island-fused kernels, the others on the dataflow launch
     bool isl_fused = false;         // every island on the island-fused kernels
     bool push = false;              // the contact sweeps hand the body deltas on through the slots (Rows::dslot)
+    bool lean = false;              // lean rows (ctx.hpp Rows::iw): a contact-only world whose velocity solve is a dataflow launch
     uint32_t lanes = 0, vel_grid = 0;   // dataflow velocity launch: lanes per manifold (0: no such launch) and workgroups
     bool pos_df = false;            // dataflow position launches ...
     uint32_t pos_grid = 0;          // ... of this many workgroups
     void set_largest(uint32_t items) { largest = items; isl_fused = isl_candidate && !mixed && largest <= kIslFusedLimit; }
-    void drop_dataflow() { lanes = 0; pos_df = false; }
+    void drop_dataflow() { lanes = 0; pos_df = false; lean = false; }
     const uint8_t *df_skip(const edynhip_ctx *c) const { return mixed ? c->rows.skip : nullptr; }
     uint32_t schedule(uint32_t num_joints) const {   // edynhip_stats::solve_schedule, once the velocity solve is enqueued
         return (na + num_joints) == 0 ? EDYNHIP_SCHEDULE_NONE
@@ -2709,6 +2773,8 @@ constexpr bool kPwInPrep = true;   // k_prep_contacts also writes the position s
 constexpr uint32_t kMixedMinFree = 1024;   // manifolds outside jointed islands that make the dataflow launch worth its fixed cost
 constexpr uint32_t kIslGrid = 4096;   // one wave each; a block takes islands blockIdx.x, + kIslGrid, ...
 
+// Lean rows are the default wherever they apply; EDYNHIP_FLAG_FULL_CONTACT_ROWS keeps every schedule on full rows (A/B, tests).
+static bool lean_rows_wanted(const edynhip_ctx *c) { return !(c->cfg.flags & EDYNHIP_FLAG_FULL_CONTACT_ROWS); }
 static SolvePlan plan_solve(const edynhip_ctx *c) {
     const Knobs &kn = c->knobs;
     const Joints &j = c->j;
@@ -2773,6 +2839,11 @@ static SolvePlan plan_solve(const edynhip_ctx *c) {
         const uint32_t want_waves = kn.df_waves ? (uint32_t)kn.df_waves : std::max(lanes == 4u ? 2048u : lanes == 2u ? 1024u : 512u, blocks(na, per_wave * 9));
         p.lanes = lanes;
         p.vel_grid = std::min(blocks(na, per_wave), std::min(resident, want_waves));
+        // Lean rows: only the dataflow velocity kernels of a contact-only world read them. Everything else that reads a row's planes 3
+        // and 4 or a normal row's .w lanes there - the per-colour kernels (also as the fallback of a refused launch: launch_velocity
+        // prepares full rows first), the serial bucket, the island kernels of the mixed and fused schedules, contact_extras - runs on
+        // schedules that never set this.
+        p.lean = lean_rows_wanted(c) && contacts_only;
     }
     // one error array per position iteration (DfPosArgs::err_out / err_prev): kMaxDfPosIters of them are allocated
     // (the dataflow position kernel hands positions and orientations over, not origins: worlds with centre-of-mass offsets solve positions per colour)
@@ -2788,10 +2859,11 @@ static SolvePlan plan_solve(const edynhip_ctx *c) {
 // (The compiler emits template kernels in the order the host code first names them, and the code it generates for OTHER kernels of this
 //  file moves with that order - k_contact_solve<true, true, true> did when k_prep_contacts<true> was first named after the position
 //  kernels. scripts/isa_identity.py compares a tree's kernels with another's.)
-static void prep_contacts(edynhip_ctx *c, uint32_t count, bool push, bool by_key, bool pw) {
+static void prep_contacts(edynhip_ctx *c, uint32_t count, bool push, bool by_key, bool pw, bool lean) {
     const Manifolds &mf = c->m[c->cur];
-    if (!c->extras) hipLaunchKernelGGL(k_prep_contacts<false>, dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
-    else hipLaunchKernelGGL(k_prep_contacts<true>, dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
+    if (!c->extras && !lean) hipLaunchKernelGGL((k_prep_contacts<false, false>), dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
+    else if (c->extras) hipLaunchKernelGGL((k_prep_contacts<true, false>), dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
+    else hipLaunchKernelGGL((k_prep_contacts<false, true>), dim3(blocks(count, 128)), dim3(128), 0, c->stream, count, c->rows, mf.cap, mf, c->b, c->cfg.fixed_dt, c->col_keys_sorted, push, by_key, pw);
 }
 
 // Islands with joints (or contact_extras rows): bucket this step's constraints by island for the island-fused kernels, and confirm the
@@ -2831,7 +2903,7 @@ static int bucket_islands(edynhip_ctx *c, SolvePlan &p) {
         if (p.isl_fused && c->cnt_host->isl_max_items > kIslFusedLimit) p.isl_fused = false;
         if (p.mixed && c->cnt_host->isl_max_jitems > kIslFusedLimit) {   // the jointed islands outgrew the fused kernels: the whole step per colour
             p.mixed = false; p.push = false; p.drop_dataflow();
-            if (na) prep_contacts(c, na, false, false, false);
+            if (na) prep_contacts(c, na, false, false, false, false);
         }
     }
     return EDYNHIP_OK;
@@ -2923,7 +2995,7 @@ static int launch_velocity(edynhip_ctx *c, SolvePlan &p, uint32_t *launches) {
         //  that were exactly as busy as the chains are long - mixed32k and pile8k win 1.5-3 % of their solves: off by default, EDYNHIP_DF_XCD=1 turns it on)
         const uint32_t xcd_lists = (kn.df_xcd && p.lanes == 2u && grid % kXcds == 0 && grid >= 8 * kXcds) ? 1u : 0u;
         DfArgs a{na, grid * per_wave, c->cfg.num_velocity_iterations + 1, c->col_keys_sorted, r.next, r.im, r.rw, c->m[c->cur].cap, r.dslot, c->cnt, nullptr, p.df_skip(c),
-                 (uint32_t)kn.df_nap, xcd_lists};   // (EDYNHIP_DF_NAP, r04 sweep on one box: 4 -> 1: +0.6 %, 0: the same)
+                 (uint32_t)kn.df_nap, xcd_lists, r.iw};   // (EDYNHIP_DF_NAP, r04 sweep on one box: 4 -> 1: +0.6 %, 0: the same)
         DfTrace trace;
         if (DfTrace::wanted(kn.df_trace, kn.df_trace_step, &c->df_solves)) {
             a.xcd_lists = 0;   // (the trace is laid out by (sweep, round, wave) of the plain assignment)
@@ -2934,13 +3006,15 @@ static int launch_velocity(edynhip_ctx *c, SolvePlan &p, uint32_t *launches) {
         void *params[] = {&a};
         // cooperative launch: the runtime guarantees that all `grid` workgroups are resident together, which the
         // hand-off polling relies on
-        if (launch_resident(c, df_velocity_fn(p.lanes, p.fused_rows), grid, 64, params) == hipSuccess) {
+        if (launch_resident(c, df_velocity_fn(p.lanes, p.fused_rows, p.lean), grid, 64, params) == hipSuccess) {
             ++*launches;
             c->paths |= (p.lanes == 4u ? EDYNHIP_PATH_VEL_LANES4 : p.lanes == 2u ? EDYNHIP_PATH_VEL_LANES2 : EDYNHIP_PATH_VEL_LANES1) | (a.xcd_lists ? EDYNHIP_PATH_VEL_XCD : 0u) |
                         (na > a.stride ? EDYNHIP_PATH_VEL_MULTI_ROUND : 0u) | (p.lanes == 2u && a.nap != 1u ? EDYNHIP_PATH_VEL_NAP : 0u);   // (only k_contact_solve_df2 reads the nap)
         } else {   // e.g. the device is shared and cannot hold the grid: use the per-colour schedule from now on
             (void)hipGetLastError();
             c->df_mode = 0;
+            // the per-colour kernels that take over read full rows: prepare them again (nothing has touched the rows or the impulses yet)
+            if (p.lean && na) prep_contacts(c, na, p.push, false, false, false);
             p.drop_dataflow();
             // the mixed schedule has no per-colour form for THIS step (the chains skip the jointed islands): give the step up,
             // the next one takes the per-colour launches
@@ -3066,11 +3140,12 @@ int solve(edynhip_ctx *c) {
     // (14 us of idle GPU per step on the headline pile, profiles/r04_timeline_pile32k.txt). If the colouring turns out unfinished
     // (uncoloured edges left for the multi-block rounds: a scene coloured from scratch) the rows are prepared again after the second sort;
     // a non-empty serial bucket only drops `push` - the slot table written for it is read through the bodies' colour masks alone.
-    bool spec_prep = false;
+    bool spec_prep = false, spec_lean = false;
     auto speculative_prep = [&]() {
         rec(c, 4);
         if (!(c->knobs.speculate && j.n == 0 && !c->extras && c->df_mode == 1 && c->full_step && c->num_manifolds > 0)) return;
-        prep_contacts(c, c->num_manifolds, true, true, kPwInPrep);
+        spec_lean = lean_rows_wanted(c);   // (what plan_solve will say unless the serial bucket turns out non-empty)
+        prep_contacts(c, c->num_manifolds, true, true, kPwInPrep, spec_lean);
         spec_prep = true;
     };
     bool first_final = false;
@@ -3085,7 +3160,8 @@ int solve(edynhip_ctx *c) {
     SolvePlan p = plan_solve(c);
     const uint32_t na = p.na;
 
-    if (na && !spec_prep) prep_contacts(c, na, p.push, false, !c->extras && kPwInPrep);
+    // (speculative lean rows and a plan that is not lean - the serial bucket, or no dataflow launch after all: prepared again in full)
+    if (na && (!spec_prep || spec_lean != p.lean)) prep_contacts(c, na, p.push, false, !c->extras && kPwInPrep, p.lean);
     if (p.isl_candidate) EH_TRY(bucket_islands(c, p));
     if (p.push) {
         hipLaunchKernelGGL(k_push_links, dim3(blocks(na, 256)), dim3(256), 0, s, na, c->rows, c->col_keys_sorted, c->b, c->used, p.mixed ? c->isl_joint : nullptr);
@@ -3096,6 +3172,7 @@ int solve(edynhip_ctx *c) {
     EH_TRY(launch_velocity(c, p, &launches));
     c->timings.solve_velocity_launches += launches;
     c->stats.solve_schedule = p.schedule(j.n);
+    c->stats.lean_rows = p.lean ? 1u : 0u;
     rec(c, 6);
 
     hipLaunchKernelGGL(k_integrate, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, dt, c->isl_err, c->isl_done, p.push ? c->rows.dslot : nullptr, c->rows.first_slot,

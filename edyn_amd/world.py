@@ -42,6 +42,7 @@ class init_config:
     # correction with the reference's operations in the reference's order; the two switches opt in to faster forms of the same equations.
     fused_velocity_rows: bool = False
     block_position: bool = False
+    full_contact_rows: bool = False   # A/B and test aid (edynhip.h EDYNHIP_FLAG_FULL_CONTACT_ROWS): no lean contact rows; the same bits either way
 
 
 @dataclass
@@ -118,7 +119,8 @@ class World:
                      | (_capi.FLAG_CONTACT_EVENTS if self.cfg.contact_events else 0)
                      | (_capi.FLAG_EXCLUSIVE_DEVICE if self.cfg.exclusive_device else 0)
                      | (_capi.FLAG_FUSED_VELOCITY_ROWS if self.cfg.fused_velocity_rows else 0)
-                     | (_capi.FLAG_BLOCK_POSITION if self.cfg.block_position else 0))
+                     | (_capi.FLAG_BLOCK_POSITION if self.cfg.block_position else 0)
+                     | (_capi.FLAG_FULL_CONTACT_ROWS if self.cfg.full_contact_rows else 0))
         st = C.c_int(0)
         h = self._L.edynhip_create(C.byref(cfg), C.byref(st))
         if not h:

@@ -89,6 +89,8 @@ enum {
                               (an algorithmic change: up to ~3e-4 m per step; SURVEY 8(d)(3) is NOT met in this mode). */
     EDYNHIP_FLAG_FUSED_VELOCITY_ROWS = 64u,
     EDYNHIP_FLAG_BLOCK_POSITION = 128u,
+    EDYNHIP_FLAG_FULL_CONTACT_ROWS = 256u, /* A/B and test aid: a contact-only world's dataflow velocity solve reads full contact rows (the stored
+                                        I^-1 J_ang planes) instead of rebuilding them from lean rows (edynhip_stats::lean_rows). Same bits either way. */
     EDYNHIP_FLAG_EXCLUSIVE_DEVICE = 8u /* promise: nothing else launches work on this device while a step runs (one stepper per
                                         GPU). The resident-grid solver kernels are then launched plainly instead of
                                         cooperatively (~0.1 ms per step less idle GPU). Without the promise the default,
@@ -181,6 +183,7 @@ typedef struct {
              num_joint_colours, colour_rounds, num_joints, num_joint_rows;   /* colour_rounds: rounds the last step's contact colouring took (the one-workgroup rounds + the multi-block ones) */
     uint32_t solve_schedule;         /* EDYNHIP_SCHEDULE_*: which velocity-solve kernels the last step launched */
     uint32_t colour_size[64];        /* manifolds per solver colour in the last step */
+    uint32_t lean_rows;              /* 1: the last step's velocity solve ran on lean contact rows */
 } edynhip_stats;
 
 /* Velocity-solve schedules (edynhip_stats::solve_schedule). The results are bit-identical across them. */
