@@ -140,7 +140,9 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            # edits of a running multi-device world
            "edynhip_world_add_bodies", "edynhip_world_remove_bodies", "edynhip_world_add_joints", "edynhip_world_remove_joints",
            "edynhip_world_edit_joint", "edynhip_world_edit_exclusion", "edynhip_world_set_state", "edynhip_world_get_params",
-           "edynhip_world_set_params", "edynhip_world_get_edit_stats", "edynhip_world_get_asleep"]
+           "edynhip_world_set_params", "edynhip_world_get_edit_stats", "edynhip_world_get_asleep",
+           # record hand-over of a multi-device world
+           "edynhip_world_snapshot_records", "edynhip_world_snapshot_map"]
 
 _lib = None
 
@@ -262,6 +264,8 @@ def lib():
         L.edynhip_world_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
         L.edynhip_world_get_edit_stats.argtypes = [C.c_void_p, C.POINTER(WorldEditStats)]
         L.edynhip_world_get_asleep.argtypes = [C.c_void_p, C.c_void_p]
+        L.edynhip_world_snapshot_records.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32]
+        L.edynhip_world_snapshot_map.argtypes = [C.c_void_p, C.POINTER(RecordView)]
         L.edynhip_partition_islands.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_island_boxes_overlap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_get_island_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]

@@ -3,6 +3,7 @@
 // broadphase.hip / narrowphase.hip / islands.hip / colouring.hip / solver.hip. There is no CPU fallback.
 #include "ctx.hpp"
 #include "dpolyhedron.hpp"
+#include "drecord.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -1736,27 +1737,11 @@ constexpr size_t kRecHeader = 64;   // [0] = events that occurred, [1] = events 
 __global__ void k_pack_records(uint32_t n, Bodies b, float present_dt, float4 *__restrict__ dst) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float4 p4 = B_POS(b, i), q4v = B_ORN(b, i), v4 = b.linvel[i], w4 = b.angvel[i];
-    const uint32_t fl = b.flags[i];
-    const f3 p = from4(p4), v = from4(v4), w = from4(w4);
-    const q4 q{q4v.x, q4v.y, q4v.z, q4v.w};
-    // update_presentation.cpp:73-79: pre = pos + vel * interpolation_dt; pre = integrate(orn, vel, interpolation_dt)
-    const f3 pp = p + v * present_dt;
-    const q4 po = integrate(q, w, present_dt);
-    const bool has_origin = b.origin && b.com[i].w != 0.0f;
-    const f3 org = has_origin ? from4(b.origin[i]) : p;
-    uint32_t rf = 0;
-    if ((fl & BF_KIND_MASK) == EDYNHIP_KIND_DYNAMIC) rf |= EDYNHIP_RECORD_DYNAMIC;
-    if (fl & BF_ASLEEP) rf |= EDYNHIP_RECORD_ASLEEP;
-    if (has_origin) rf |= EDYNHIP_RECORD_HAS_ORIGIN;
-    if (fl & BF_REMOVED) rf |= EDYNHIP_RECORD_REMOVED;
+    float4 rec[6];
+    body_record(b, i, present_dt, rec);   // drecord.hpp: shared with the multi-device world's pack
     float4 *o = dst + (size_t)i * 6;
-    o[0] = make_float4(p.x, p.y, p.z, q.x);
-    o[1] = make_float4(q.y, q.z, q.w, v.x);
-    o[2] = make_float4(v.y, v.z, w.x, w.y);
-    o[3] = make_float4(w.z, pp.x, pp.y, pp.z);
-    o[4] = make_float4(po.x, po.y, po.z, po.w);
-    o[5] = make_float4(org.x, org.y, org.z, __uint_as_float(rf));
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = rec[k];
 }
 __global__ void k_pack_events(const eh::ContactEvent *__restrict__ events, const uint32_t *__restrict__ count, uint32_t cap, uint32_t max_copy,
                               uint32_t *__restrict__ header, eh::ContactEvent *__restrict__ dst) {

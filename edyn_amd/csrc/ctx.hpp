@@ -550,6 +550,9 @@ constexpr uint32_t kEventTagShift = 28, kEventTagShards = 16;   // id low word: 
 int shard_translate_events(edynhip_ctx *c, uint32_t expected, const uint32_t *local_ids_dev, uint32_t n_local, void *out);
 int shard_gather_point_ids(edynhip_ctx *c, uint64_t *ids_dev);
 int shard_inject_point_ids(edynhip_ctx *c, const uint64_t *ids_dev, uint32_t num_manifolds);
+// world_records.hip: the registry records (edynhip_body_record) of the bodies this shard reports (`answers`), stored at their global
+// indices into records[num_bodies] - the world's pinned slot, mapped into this device
+int shard_pack_records(edynhip_ctx *c, const uint32_t *local_ids_dev, uint32_t n_local, uint32_t num_bodies, float present_dt, void *records);
 }  // namespace eh
 
 #define EH_HIP(c, call)                                                          \

@@ -234,6 +234,28 @@ class MultiWorld:
             self._check(self._L.edynhip_world_get_point_ids(self._h, _ptr(out), m.value, C.byref(m)))
         return out[:m.value]
 
+    # ---- record hand-over: World.snapshot_records / .snapshot_map on the whole world (edynhip_world_snapshot_records / _map)
+    def snapshot_records(self, present_dt=0.0, max_events=4096):
+        """One 96-byte record per body (global order) and the last step call's contact events into one of the world's two pinned slots;
+        every shard's device stores its own bodies' records there."""
+        self._check(self._L.edynhip_world_snapshot_records(self._h, float(present_dt), int(max_events), 0))
+
+    def snapshot_view(self):
+        """The raw edynhip_record_view of the last snapshot (pointers into the pinned slot, valid until the next-but-one snapshot_records)."""
+        v = _capi.RecordView()
+        self._check(self._L.edynhip_world_snapshot_map(self._h, C.byref(v)))
+        return v
+
+    def snapshot_map(self):
+        """(records, events, total_events, step_index): structured COPIES of the pinned slot, as World.snapshot_map returns them."""
+        v = self.snapshot_view()
+        rec = np.ctypeslib.as_array((C.c_uint8 * (v.num_bodies * _capi.RECORD_DTYPE.itemsize)).from_address(v.records)).view(_capi.RECORD_DTYPE).copy() \
+            if v.num_bodies else np.zeros(0, _capi.RECORD_DTYPE)
+        ev = np.zeros(0, _capi.EVENT_DTYPE)
+        if v.events and v.num_events:
+            ev = np.ctypeslib.as_array((C.c_uint8 * (v.num_events * _capi.EVENT_DTYPE.itemsize)).from_address(v.events)).view(_capi.EVENT_DTYPE).copy()
+        return rec, ev, int(v.total_events), int(v.step_index)
+
     # ---- queries: World.raycast / World.query_aabb on the whole world, global body indices (edynhip_world_raycast / _query_aabb)
     def raycast(self, p0, p1, ignore=(), brute_force=False):
         """Rays p0[i] -> p1[i] (arrays of shape (n, 3), or one ray of shape (3,)); returns a RAYCAST_HIT_DTYPE array of n records, bit for

@@ -242,9 +242,12 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
     int device{0};
     // More than one entry: ONE simulation over these GPUs at island granularity (edynhip.h "Multi-GPU world": one shard per device,
     // islands partitioned by load, re-partitioned when islands of different shards meet) - the reference's island parallelism
-    // (solver.cpp:408-428) across devices. Bodies of every shape, every constraint type, exclusions and settings are supported;
-    // contact entities, contact_extras materials / the mix table, asynchronous mode and step callbacks are single-device features
-    // (attach throws stepper_error EDYNHIP_ERR_UNSUPPORTED when combined). An edit of a running multi-device world is forwarded to
+    // (solver.cpp:408-428) across devices. Bodies of every shape, every constraint type, exclusions, settings, contact entities
+    // (materialize_contacts, contact_point_data, edyn::refresh_contact_points, manifold_exists, visit_edges) and step callbacks in the
+    // sequential modes are supported: the write-back reads the world's record hand-over in place (edynhip_world_snapshot_records), so
+    // state, presentation, sleeping tags and contact events arrive as they do from one device. Still single-device features (a
+    // stepper_error EDYNHIP_ERR_UNSUPPORTED when combined): execution_mode::asynchronous, contact_extras materials, material ids and
+    // the mix table, edyn::raycast and the AABB queries. An edit of a running multi-device world is forwarded to
     // the world as it is to one context (edynhip.h "Edits of a RUNNING multi-device world"): bodies and constraints made after attach,
     // their definitions, exclude_collision, registry.destroy of either, edyn::refresh and settings changes keep every contact's warm
     // start, the joints' impulses and angles, sleep timers and the step count - the registry program computes what it computes on one
@@ -690,7 +693,7 @@ inline void upload_joint_defs(entt::registry &registry, gpu_stepper &s, uint32_t
 // Everything else is appended to / edited on the running world (append_scene_multi, upload_state_multi, apply_params_multi, sync_removed).
 inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     const uint32_t total = (uint32_t)s.bodies.size(), nj = (uint32_t)s.constraints.size();
-    if (s.world) { edynhip_world_destroy(s.world); s.world = nullptr; }
+    if (s.world) { edynhip_world_destroy(s.world); s.world = nullptr; s.contacts_resync = true; }   // a new world issues new point ids: the contact entities are rebuilt
     if (!s.mixings.empty()) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: the material mix table is a single-device feature (init_config::devices)");
     edynhip_config c{};
     c.max_manifolds = s.cfg.max_manifolds;
@@ -698,7 +701,8 @@ inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     c.num_velocity_iterations = s.cfg.num_solver_velocity_iterations;
     c.num_position_iterations = s.cfg.num_solver_position_iterations;
     c.gravity[0] = s.cfg.gravity.x; c.gravity[1] = s.cfg.gravity.y; c.gravity[2] = s.cfg.gravity.z;
-    c.flags = (s.cfg.island_sleeping ? EDYNHIP_FLAG_SLEEPING : 0u) | (s.cfg.fused_velocity_rows ? EDYNHIP_FLAG_FUSED_VELOCITY_ROWS : 0u) | (s.cfg.block_position ? EDYNHIP_FLAG_BLOCK_POSITION : 0u);
+    c.flags = (s.cfg.island_sleeping ? EDYNHIP_FLAG_SLEEPING : 0u) | (s.cfg.materialize_contacts ? EDYNHIP_FLAG_CONTACT_EVENTS : 0u) |
+              (s.cfg.fused_velocity_rows ? EDYNHIP_FLAG_FUSED_VELOCITY_ROWS : 0u) | (s.cfg.block_position ? EDYNHIP_FLAG_BLOCK_POSITION : 0u);
     std::vector<int32_t> devs(s.cfg.devices.begin(), s.cfg.devices.end());
     int st = 0;
     s.world = edynhip_world_create(&c, devs.data(), (uint32_t)devs.size(), &st);
@@ -1052,6 +1056,24 @@ inline void write_back(entt::registry &registry, gpu_stepper &s, bool presentati
     { phase_timer t(s.tm.write_back); import_records(registry, s, view, presentation); }
 }
 
+// The same write-back on a multi-device world (init_config::devices): the world's record hand-over read in place - every shard's device
+// stores its bodies' records into the world's pinned slot - and the step call's contact events from the view. A list that was cut
+// (total_events > num_events) rebuilds the contact entities from the world's manifolds and point ids.
+inline void write_back_world(entt::registry &registry, gpu_stepper &s, bool presentation) {
+    { phase_timer t(s.tm.state_wait); check(s, edynhip_world_snapshot_records(s.world, s.present_dt, s.cfg.materialize_contacts ? 0xFFFFFFFFu : 0u, EDYNHIP_SNAPSHOT_DIRECT)); }
+    pool_of(s).prewake();
+    edynhip_record_view view{};
+    { phase_timer t(s.tm.state_wait); check(s, edynhip_world_snapshot_map(s.world, &view)); }
+    if (s.cfg.materialize_contacts) {
+        phase_timer t(s.tm.contacts);
+        std::vector<edynhip_contact_event> ev;
+        if (view.total_events > view.num_events) s.contacts_resync = true;
+        else if (view.num_events) ev.assign(view.events, view.events + view.num_events);
+        apply_contact_events(registry, s, ev, EDYNHIP_OK);
+    }
+    { phase_timer t(s.tm.write_back); import_records(registry, s, view, presentation); }
+}
+
 // registry.destroy(entity) / clear_rigidbody on bodies and constraints since the last update: the reference reacts through
 // on_destroy hooks (island_manager.cpp:24-27); this shim notices at the next update that the entity is gone (or no longer
 // carries the component that made it a body / a joint) and removes it from the device world, keeping every other index.
@@ -1110,14 +1132,27 @@ inline void apply_params(gpu_stepper &s) {   // settings on the running context 
 // contact_manifold entity per overlapping pair (make_contact_manifold, constraint_util.cpp:60-102), a contact_point entity
 // per point (create_contact_point, collision_util.cpp:311-388), destroyed when the device says so.
 inline uint64_t manifold_key(uint32_t a, uint32_t b) { return ((uint64_t)a << 32) | b; }
-inline void refresh_contact_points(entt::registry &registry, gpu_stepper &s) {
+// Where manifolds, point ids and events come from: the context, or the multi-device world (init_config::devices) - the same records in
+// global body indices. Everything below (refresh_contact_points, apply_contact_events, sync_contacts) is written once over these two.
+inline bool has_device_world(const gpu_stepper &s) { return s.ctx != nullptr || s.world != nullptr; }
+inline void fetch_manifolds(gpu_stepper &s, std::vector<edynhip_manifold> &recs, std::vector<uint64_t> &ids) {
+    recs.clear(); ids.clear();
+    if (!has_device_world(s)) return;   // (nothing uploaded yet: no manifolds)
     uint32_t n = 0;
-    check(s, edynhip_num_manifolds(s.ctx, &n));
+    check(s, s.world ? edynhip_world_get_manifolds(s.world, nullptr, 0, &n) : edynhip_num_manifolds(s.ctx, &n));
+    recs.resize(n); ids.assign((size_t)4 * n, 0);
     if (n == 0) return;
-    std::vector<edynhip_manifold> recs(n);
-    std::vector<uint64_t> ids((size_t)4 * n);
-    check(s, edynhip_get_manifolds(s.ctx, recs.data(), n, &n));
-    check(s, edynhip_get_point_ids(s.ctx, ids.data(), n, &n));
+    check(s, s.world ? edynhip_world_get_manifolds(s.world, recs.data(), n, &n) : edynhip_get_manifolds(s.ctx, recs.data(), n, &n));
+    check(s, s.world ? edynhip_world_get_point_ids(s.world, ids.data(), n, &n) : edynhip_get_point_ids(s.ctx, ids.data(), n, &n));
+}
+inline int fetch_contact_events(gpu_stepper &s, edynhip_contact_event *out, uint32_t capacity, uint32_t *n) {
+    return s.world ? edynhip_world_get_contact_events(s.world, out, capacity, n) : edynhip_get_contact_events(s.ctx, out, capacity, n);
+}
+inline void refresh_contact_points(entt::registry &registry, gpu_stepper &s) {
+    std::vector<edynhip_manifold> recs;
+    std::vector<uint64_t> ids;
+    fetch_manifolds(s, recs, ids);
+    const uint32_t n = (uint32_t)recs.size();
     for (uint32_t m = 0; m < n; ++m)
         for (uint32_t k = 0; k < recs[m].num_points; ++k) {
             auto it = s.point_entities.find(ids[(size_t)4 * m + k]);
@@ -1129,7 +1164,7 @@ inline void refresh_contact_points(entt::registry &registry, gpu_stepper &s) {
         }
 }
 inline void apply_contact_events(entt::registry &registry, gpu_stepper &s, std::vector<edynhip_contact_event> &ev, int rc) {
-    if (!s.cfg.materialize_contacts || !s.ctx) return;
+    if (!s.cfg.materialize_contacts) return;
     s.tm.contact_events += ev.size();
     if (ev.empty() && rc == EDYNHIP_OK && !s.contacts_resync) { if (s.cfg.contact_point_data) refresh_contact_points(registry, s); return; }
     auto body_of = [&](uint32_t i) { return i < s.bodies.size() ? s.bodies[i] : entt::entity{entt::null}; };
@@ -1161,11 +1196,10 @@ inline void apply_contact_events(entt::registry &registry, gpu_stepper &s, std::
         for (auto &kv : s.point_entities) registry.destroy(kv.second);
         for (auto &kv : s.manifold_entities) registry.destroy(kv.second);
         s.point_entities.clear(); s.manifold_entities.clear();
-        uint32_t m = 0;
-        check(s, edynhip_num_manifolds(s.ctx, &m));
-        std::vector<edynhip_manifold> recs(m);
-        std::vector<uint64_t> ids((size_t)4 * m);
-        if (m) { check(s, edynhip_get_manifolds(s.ctx, recs.data(), m, &m)); check(s, edynhip_get_point_ids(s.ctx, ids.data(), m, &m)); }
+        std::vector<edynhip_manifold> recs;
+        std::vector<uint64_t> ids;
+        fetch_manifolds(s, recs, ids);
+        const uint32_t m = (uint32_t)recs.size();
         for (uint32_t i = 0; i < m; ++i) {
             make_manifold(recs[i].body[0], recs[i].body[1]);
             for (uint32_t k = 0; k < recs[i].num_points; ++k) make_point(recs[i].body[0], recs[i].body[1], ids[(size_t)4 * i + k]);
@@ -1204,11 +1238,11 @@ inline void apply_contact_events(entt::registry &registry, gpu_stepper &s, std::
     if (s.cfg.contact_point_data) refresh_contact_points(registry, s);
 }
 inline void sync_contacts(entt::registry &registry, gpu_stepper &s) {   // the events straight from the device (no record snapshot at hand)
-    if (!s.cfg.materialize_contacts || !s.ctx) return;
+    if (!s.cfg.materialize_contacts || !has_device_world(s)) return;
     uint32_t n = 0;
-    int rc = edynhip_get_contact_events(s.ctx, nullptr, 0, &n);
+    int rc = fetch_contact_events(s, nullptr, 0, &n);
     std::vector<edynhip_contact_event> ev(n);
-    if (rc == EDYNHIP_OK && n) rc = edynhip_get_contact_events(s.ctx, ev.data(), n, &n);
+    if (rc == EDYNHIP_OK && n) rc = fetch_contact_events(s, ev.data(), n, &n);
     apply_contact_events(registry, s, ev, rc);
 }
 inline void import_state(entt::registry &registry, gpu_stepper &s, const std::vector<float> &pos, const std::vector<float> &orn,
@@ -1290,22 +1324,31 @@ inline void run_steps(entt::registry &registry, gpu_stepper &s, unsigned steps, 
         s.records_pending = false;
     }
     if (s.multi()) {   // init_config::devices: the multi-GPU world (see upload_scene_multi)
-        if (async || s.pre_step || s.post_step || s.cfg.contact_point_data)
-            throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: asynchronous mode, step callbacks and contact entities are single-device features (init_config::devices)");
+        if (async) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: execution_mode::asynchronous is a single-device feature (init_config::devices)");
         // the single-device sequence on the running world: removals, what was made since the last upload, the edited state, the settings
-        sync_removed(registry, s);
+        { phase_timer t(s.tm.sync_removed); sync_removed(registry, s); }
         if (s.bodies.empty()) return;
-        if (!s.world || s.recreate) upload_scene_multi(registry, s);
-        else if (s.scene_dirty) append_scene_multi(registry, s);
-        if (s.state_dirty) upload_state(registry, s);
-        apply_params(s);
-        if (steps == 0) return;
-        check(s, edynhip_world_step(s.world, steps));
-        const uint32_t n = (uint32_t)s.bodies.size();
-        std::vector<float> pos(3 * (size_t)n), orn(4 * (size_t)n), lv(3 * (size_t)n), av(3 * (size_t)n);
-        check(s, edynhip_world_get_state(s.world, pos.data(), orn.data(), lv.data(), av.data()));
-        import_state(registry, s, pos, orn, lv, av, n);
-        s.host_presentation = true;   // (the multi-GPU world hands back plain state arrays)
+        {
+            phase_timer t(s.tm.upload);
+            if (!s.world || s.recreate) upload_scene_multi(registry, s);
+            else if (s.scene_dirty) append_scene_multi(registry, s);
+            if (s.state_dirty) upload_state(registry, s);
+            apply_params(s);
+        }
+        if (steps == 0) { s.host_presentation = true; return; }   // time went on without a step: presentation from the registry's state, as on one device
+        s.tm.steps += steps;
+        if (s.pre_step || s.post_step) {   // one step per call, the write-back after each, a callback's edits uploaded before the next: as on one device
+            for (unsigned k = 0; k < steps; ++k) {
+                if (s.pre_step) s.pre_step(registry);
+                if (s.state_dirty) upload_state(registry, s);
+                check(s, edynhip_world_step(s.world, 1));
+                write_back_world(registry, s, s.present_this_call && k + 1 == steps);
+                if (s.post_step) s.post_step(registry);
+            }
+            return;
+        }
+        { phase_timer t(s.tm.step_call); check(s, edynhip_world_step(s.world, steps)); }
+        write_back_world(registry, s, s.present_this_call);
         return;
     }
     { phase_timer t(s.tm.sync_removed); sync_removed(registry, s); }
@@ -1366,8 +1409,8 @@ inline scalar presentation_dt(const gpu_stepper &s, double time) {
     const double sim_time = time - s.accumulated;   // get_simulation_timestamp() once m_last_time = time
     return std::min(static_cast<scalar>(time - s.cfg.fixed_dt - sim_time), s.cfg.fixed_dt);
 }
-// The host form of update_presentation: used when the update ran no step (time went on, the state did not) and by the multi-GPU
-// world; an update that steps gets the same transforms from the device with the state (edynhip_body_record::present_*).
+// The host form of update_presentation: used when the update ran no step (time went on, the state did not); an update that steps
+// gets the same transforms from the device with the state (edynhip_body_record::present_*), on one device and on several.
 inline void update_presentation(entt::registry &registry, gpu_stepper &s, scalar idt) {
     const uint32_t n = (uint32_t)s.bodies.size();
     auto &sp = registry.storage<position>(); auto &sq = registry.storage<orientation>();
@@ -2137,7 +2180,7 @@ inline void insert_material_mixing(entt::registry &registry, material::id_type i
 /// Refreshes pivots / normal / distance / impulses of every contact_point entity from the device (one read-back).
 inline void refresh_contact_points(entt::registry &registry) {
     auto &s = registry.ctx().get<detail::gpu_stepper>();
-    if (s.ctx && s.cfg.materialize_contacts) detail::refresh_contact_points(registry, s);
+    if (detail::has_device_world(s) && s.cfg.materialize_contacts) detail::refresh_contact_points(registry, s);
 }
 
 /// Current contact manifolds (body pair + point count), materialised on demand.

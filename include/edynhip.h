@@ -584,8 +584,8 @@ int edynhip_measure_bandwidth(edynhip_ctx *ctx, uint64_t bytes, float *read_gbs,
  * init_config::devices (include/edyn/edyn.hpp of this repository; the reference's attach: include/edyn/edyn.hpp:66-70).
  * Every device gets one edynhip_ctx (a "shard") that owns the dynamic bodies of its islands plus a replica of every non-dynamic
  * body; shards step concurrently (one private host thread each) with NO exchange inside a step; after each step the integrated
- * state of every shard is copied into pinned host memory and from there into the world's arrays (edynhip_world_get_state) - the
- * registry write-back. Islands of different shards that approach each other are noticed from island bounding boxes reduced ON
+ * state of every shard is copied into pinned host memory and from there into the world's arrays (edynhip_world_get_state); the
+ * registry write-back reads edynhip_world_snapshot_records' records in place (below). Islands of different shards that approach each other are noticed from island bounding boxes reduced ON
  * THE DEVICE (edyn_amd/csrc/multi.hip), and the world re-partitions, carrying contact manifolds (warm-start impulses, colours),
  * joint impulses / angles, sleeping tags, exclusions, joint definitions and meshes to the islands' new owners. A shard computes
  * for its islands bit for bit what one context computes for the whole world (tests/cpp/multi.cpp).
@@ -723,6 +723,25 @@ int edynhip_world_get_edit_stats(edynhip_world *w, edynhip_world_edit_stats *out
 /* edynhip_get_asleep on the whole world (additive to ABI 15): asleep[num_bodies], every body's sleeping_tag from the shard that reports
  * its state; all 0 without EDYNHIP_FLAG_SLEEPING. (With tombstones in the world the partition no longer tells which bodies a shard holds.) */
 int edynhip_world_get_asleep(edynhip_world *w, uint8_t *asleep);
+/* edynhip_snapshot_records / edynhip_snapshot_map on a multi-device world (additive to ABI 15): the registry write-back read in place.
+ * Same edynhip_record_view, same contract, and - record for record, byte for byte - what ONE context holding the whole scene hands over:
+ *   records[num_bodies]  by GLOBAL body index. Every shard packs the bodies it reports (its own dynamic bodies; shard 0 also the replicated
+ *                        ones) with the single context's record arithmetic and stores them straight into the world's pinned slot, which
+ *                        is allocated portable and mapped so that every shard's device writes into it (edyn_amd/csrc/world_records.hip);
+ *                        a removed body keeps its tombstone record (EDYNHIP_RECORD_REMOVED) whichever shard holds the slot.
+ *   step_index           the world's steps since edynhip_world_set_bodies.
+ *   events               the first min(max_events, n) records of edynhip_world_get_contact_events' list for the last edynhip_world_step call,
+ *                        same order, same bytes, copied from devices[0] after the shards' appends; NULL on a world created without
+ *                        EDYNHIP_FLAG_CONTACT_EVENTS. total_events = the events that occurred - the sum of what the shards counted, also
+ *                        where a shard's own list overflowed - so total_events > num_events exactly when the list was cut anywhere:
+ *                        resynchronise from edynhip_world_get_manifolds + edynhip_world_get_point_ids then.
+ * edynhip_world_snapshot_records enqueues the packs behind the steps issued so far (edynhip_world_step returns with the shards idle) and
+ * returns; edynhip_world_snapshot_map waits for THAT snapshot only. The world owns two slots, used alternately: the pointers stay valid
+ * until the next-but-one edynhip_world_snapshot_records call; a slot grows (and may move) when it is reused for more bodies or events.
+ * flags: 0 or EDYNHIP_SNAPSHOT_DIRECT - both store directly into the pinned slot; anything else: EDYNHIP_ERR_INVALID. A map before any
+ * snapshot: EDYNHIP_ERR_INVALID. A world that is described but not stepped builds its shards first and hands over the described state. */
+int edynhip_world_snapshot_records(edynhip_world *w, float present_dt, uint32_t max_events, uint32_t flags);
+int edynhip_world_snapshot_map(edynhip_world *w, edynhip_record_view *view);
 /* edynhip_debug_paths of a multi-device world (additive to ABI 15): the OR over every shard context the world has had, plus
  * EDYNHIP_PATH_WORLD_SERIAL when the shards were stepped one after the other on the caller's thread. */
 int edynhip_world_debug_paths(edynhip_world *w, uint64_t *mask);
