@@ -19,8 +19,12 @@
 // Body order inside a shard is ascending global index, so canonical pair keys, island labels (lowest index) and the colouring keep
 // their relative order: a shard computes for its islands exactly what one context computes for the whole world
 // (tests/cpp/multi.cpp: bit-equal through a forced and an approach-triggered re-partition).
+//
+// The rules that decide where things live - islands, partitioners, box sweep, welding, sticky targets, rebalance, placement, ownership -
+// are plain C++ in world_rules.hpp; this file holds the world, its shards and everything that touches a device.
 #include "ctx.hpp"
 #include "world_query.hpp"
+#include "world_rules.hpp"
 #include <chrono>
 #include <algorithm>
 #include <atomic>
@@ -34,140 +38,6 @@
 #include <unordered_map>
 
 namespace eh {
-
-// ------------------------------------------------------------------------------------------------ host-only pieces
-// Longest-processing-time-first: islands by descending weight (ties: ascending label), each to the lightest rank so far (ties: the
-// lowest rank). rank_of[i] = -1 for bodies that are not dynamic (replicated on every rank).
-static void partition_islands(uint32_t n, const uint32_t *labels, const int32_t *kind, const double *weights, uint32_t world_size, int32_t *rank_of) {
-    std::vector<uint32_t> isl;
-    isl.reserve(1024);
-    for (uint32_t i = 0; i < n; ++i) { rank_of[i] = -1; if (kind[i] == EDYNHIP_KIND_DYNAMIC) isl.push_back(labels[i]); }
-    std::sort(isl.begin(), isl.end());
-    isl.erase(std::unique(isl.begin(), isl.end()), isl.end());
-    const uint32_t m = (uint32_t)isl.size();
-    if (m == 0) return;
-    auto index_of = [&](uint32_t label) { return (uint32_t)(std::lower_bound(isl.begin(), isl.end(), label) - isl.begin()); };
-    std::vector<double> w(m, 0.0);
-    for (uint32_t i = 0; i < n; ++i) if (kind[i] == EDYNHIP_KIND_DYNAMIC) w[index_of(labels[i])] += weights ? weights[i] : 1.0;
-    std::vector<uint32_t> order(m);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return w[a] != w[b] ? w[a] > w[b] : isl[a] < isl[b]; });
-    std::vector<double> load(world_size, 0.0);
-    std::vector<int32_t> owner(m, 0);
-    for (uint32_t k : order) {
-        uint32_t r = 0;
-        for (uint32_t q = 1; q < world_size; ++q) if (load[q] < load[r]) r = q;
-        owner[k] = (int32_t)r;
-        load[r] += w[k];
-    }
-    for (uint32_t i = 0; i < n; ++i) if (kind[i] == EDYNHIP_KIND_DYNAMIC) rank_of[i] = owner[index_of(labels[i])];
-}
-
-// The world's own placement rule (round 5): islands in the order of a space-filling curve through their box centres (30-bit Morton
-// keys over the scene's bounds), cut into world_size runs of equal weight. Neighbours in space mostly share a shard, so islands that
-// meet later mostly meet inside a shard - the longest-processing-time rule above scatters neighbours over the shards, and every meeting
-// of two of them then costs a re-partition (a field of collapsing piles: 18 in 40 steps). A shard's load is within one island of the mean.
-// aabb6[n][6]: the bodies' boxes; shapeless bodies count with a point at the origin of their island's other bodies (or 0).
-static void partition_islands_spatial(uint32_t n, const uint32_t *labels, const int32_t *kind, const double *weights, const float *aabb6, uint32_t world_size, int32_t *rank_of) {
-    std::vector<uint32_t> isl;
-    for (uint32_t i = 0; i < n; ++i) { rank_of[i] = -1; if (kind[i] == EDYNHIP_KIND_DYNAMIC) isl.push_back(labels[i]); }
-    std::sort(isl.begin(), isl.end());
-    isl.erase(std::unique(isl.begin(), isl.end()), isl.end());
-    const uint32_t m = (uint32_t)isl.size();
-    if (m == 0) return;
-    auto index_of = [&](uint32_t label) { return (uint32_t)(std::lower_bound(isl.begin(), isl.end(), label) - isl.begin()); };
-    std::vector<double> w(m, 0.0), cx(3 * (size_t)m, 0.0), cw(m, 0.0);
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (uint32_t i = 0; i < n; ++i) {
-        if (kind[i] != EDYNHIP_KIND_DYNAMIC) continue;
-        const uint32_t k = index_of(labels[i]);
-        w[k] += weights ? weights[i] : 1.0;
-        const float *b = aabb6 + 6 * (size_t)i;
-        bool finite = true;
-        for (int d = 0; d < 6; ++d) finite = finite && std::isfinite(b[d]) && std::fabs(b[d]) < 1.0e30f;
-        if (!finite || (b[0] == 0 && b[3] == 0 && b[1] == 0 && b[4] == 0 && b[2] == 0 && b[5] == 0)) continue;   // no shape: no place of its own
-        for (int d = 0; d < 3; ++d) { cx[3 * (size_t)k + d] += 0.5 * ((double)b[d] + (double)b[3 + d]); }
-        cw[k] += 1.0;
-    }
-    // islands without any shaped body have no place: they stay out of the bounds the Morton keys are quantised over (a scene far from the
-    // origin would otherwise lose its resolution to a phantom island at 0,0,0) and take the key of the scene's lower corner
-    for (uint32_t k = 0; k < m; ++k) for (int d = 0; d < 3; ++d) {
-        if (cw[k] <= 0) continue;
-        cx[3 * (size_t)k + d] /= cw[k];
-        lo[d] = std::min(lo[d], cx[3 * (size_t)k + d]); hi[d] = std::max(hi[d], cx[3 * (size_t)k + d]);
-    }
-    for (uint32_t k = 0; k < m; ++k) if (cw[k] <= 0) for (int d = 0; d < 3; ++d) cx[3 * (size_t)k + d] = lo[d] <= hi[d] ? lo[d] : 0.0;
-    for (int d = 0; d < 3; ++d) if (lo[d] > hi[d]) lo[d] = hi[d] = 0.0;
-    auto spread = [](uint32_t v) { v &= 0x3FFu; v = (v | (v << 16)) & 0x030000FFu; v = (v | (v << 8)) & 0x0300F00Fu; v = (v | (v << 4)) & 0x030C30C3u; v = (v | (v << 2)) & 0x09249249u; return v; };
-    std::vector<uint32_t> key(m), order(m);
-    for (uint32_t k = 0; k < m; ++k) {
-        uint32_t q[3];
-        for (int d = 0; d < 3; ++d) { const double ext = hi[d] - lo[d]; q[d] = ext > 0 ? (uint32_t)std::min(1023.0, (cx[3 * (size_t)k + d] - lo[d]) / ext * 1024.0) : 0u; }
-        key[k] = spread(q[0]) | (spread(q[1]) << 1) | (spread(q[2]) << 2);
-    }
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] != key[b] ? key[a] < key[b] : isl[a] < isl[b]; });
-    double total = 0, before = 0;
-    for (double x : w) total += x;
-    std::vector<int32_t> owner(m, 0);
-    for (uint32_t k : order) {   // the run an island falls into is decided by the middle of its own weight interval
-        const double mid = before + 0.5 * w[k];
-        owner[k] = (int32_t)std::min<double>(world_size - 1, std::floor(mid / total * world_size));
-        before += w[k];
-    }
-    for (uint32_t i = 0; i < n; ++i) if (kind[i] == EDYNHIP_KIND_DYNAMIC) rank_of[i] = owner[index_of(labels[i])];
-}
-
-struct IslandBox { float lo[3], hi[3]; uint32_t label; int32_t owner; };
-// Sweep along x over boxes grown by `reach` on every side: calls hit(a, b, gap) for every pair whose grown boxes overlap, gap = the
-// largest per-axis distance between the ORIGINAL boxes (0 when they overlap). cross_only: pairs of different owners only.
-template <typename Hit>
-static void sweep_boxes(std::vector<IslandBox> &boxes, float reach, bool cross_only, Hit &&hit) {
-    // Sweep along x; the boxes still open at the sweep front are kept in BUCKETS along z, so a box only meets the open boxes of the z
-    // cells it reaches. (Round 6: with one list of open boxes a field of piles on a 64 x 64 grid - 262 144 body boxes, every pile of a
-    // column open at once - cost ~260 M pair tests, 0.8 s of every re-partition's 1.2 s.) A pair that shares several cells is tested in
-    // the first of them only.
-    std::sort(boxes.begin(), boxes.end(), [](const IslandBox &a, const IslandBox &b) { return a.lo[0] != b.lo[0] ? a.lo[0] < b.lo[0] : a.label < b.label; });
-    const uint32_t nb = (uint32_t)boxes.size();
-    if (nb < 2) return;
-    float zlo = 3.0e38f, zhi = -3.0e38f;
-    double ext = 0;
-    uint32_t finite = 0;
-    for (const IslandBox &b : boxes) {
-        if (!(b.lo[2] <= b.hi[2]) || !std::isfinite(b.lo[2]) || !std::isfinite(b.hi[2])) continue;
-        zlo = std::min(zlo, b.lo[2]); zhi = std::max(zhi, b.hi[2]); ext += (double)b.hi[2] - (double)b.lo[2]; ++finite;
-    }
-    const float mean_ext = finite ? (float)(ext / finite) : 0.0f;
-    const float span = finite ? zhi - zlo : 0.0f;
-    const uint32_t cells = span > 0 ? (uint32_t)std::min(4096.0f, std::max(1.0f, span / std::max(mean_ext + 2 * reach, 1e-3f))) : 1u;
-    const float inv = cells > 1 ? (float)cells / span : 0.0f;
-    auto cell_of = [&](float z) { if (!(z > zlo)) return 0u; const float c = (z - zlo) * inv; return c >= (float)(cells - 1) ? cells - 1 : (uint32_t)c; };   // (NaN and -inf land in cell 0, +inf in the last)
-    std::vector<std::vector<uint32_t>> open(cells);
-    std::vector<uint32_t> first_cell(nb);
-    for (uint32_t k = 0; k < nb; ++k) {
-        const IslandBox &bk = boxes[k];
-        const bool sane = bk.lo[2] <= bk.hi[2];
-        const uint32_t q0 = sane ? cell_of(bk.lo[2] - 2 * reach) : 0u, q1 = sane ? cell_of(bk.hi[2] + 2 * reach) : cells - 1;
-        for (uint32_t c = q0; c <= q1; ++c) {
-            std::vector<uint32_t> &bucket = open[c];
-            size_t keep = 0;
-            for (uint32_t a : bucket) {
-                const IslandBox &ba = boxes[a];
-                if (!(ba.hi[0] + 2 * reach >= bk.lo[0])) continue;   // the sweep front has passed it: drop it from this bucket
-                bucket[keep++] = a;
-                if (c != std::max(first_cell[a], q0)) continue;       // this pair is tested in the first cell the two share
-                if (cross_only && ba.owner == bk.owner) continue;
-                float gap = 0;
-                for (int d = 0; d < 3; ++d) gap = std::max(gap, std::max(bk.lo[d] - ba.hi[d], ba.lo[d] - bk.hi[d]));
-                if (gap < 2 * reach) hit(ba, bk, gap);
-            }
-            bucket.resize(keep);
-        }
-        const uint32_t i0 = sane ? cell_of(bk.lo[2]) : 0u, i1 = sane ? cell_of(bk.hi[2]) : cells - 1;
-        first_cell[k] = i0;
-        for (uint32_t c = i0; c <= i1; ++c) open[c].push_back(k);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ device pieces
 __device__ __forceinline__ uint32_t ordered_bits(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -333,8 +203,6 @@ private:
     bool stop_ = false;
 };
 
-constexpr float kCreationMargin = 0.026f;   // broadphase.hpp:18: a manifold exists once two AABBs are this close; both boxes are grown by it
-constexpr float kHorizon = 1.0f;            // cross-shard pairs further apart than this are not tracked individually
 
 }  // namespace
 
@@ -533,6 +401,62 @@ struct PhaseTrace {
         t0 = t1;
     }
 };
+
+// An edit's or a getter's work on the shards, on their threads: every shard starts with its error cleared; `work(s, r)` runs on the
+// shards that `wants(s, r)` names, with the shard's device current. Returns the first shard's error.
+template <typename Wants, typename Work>
+int on_shards(edynhip_world *w, Wants &&wants, Work &&work) {
+    w->pool->run([&](uint32_t r) {
+        Shard &s = w->shards[r];
+        s.rc = EDYNHIP_OK; s.err.clear();
+        if (!wants(s, r)) return;
+        SH_HIP(s, hipSetDevice(s.device));
+        work(s, r);
+    });
+    return shard_error(w);
+}
+
+void refresh_bodies_per_shard(edynhip_world *w) {
+    for (uint32_t r = 0; r < w->shards.size(); ++r) w->stats.bodies_per_shard[r < 16 ? r : 15] = (uint32_t)w->shards[r].owned_local.size();
+}
+
+// the three island-box kernels over the monitor scratch `d` of n bodies (k_island_box_*), behind a clear of the growth bits and the count
+hipError_t launch_island_boxes(hipStream_t st, uint32_t n, const Bodies &b, uint32_t *d, const MonLayout &L, bool per_body) {
+    const hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(uint32_t), st);
+    hipLaunchKernelGGL(k_island_box_clear, dim3((3 * n + 255) / 256), dim3(256), 0, st, n, d + L.lo, d + L.hi);
+    hipLaunchKernelGGL(k_island_box_reduce, dim3((n + 255) / 256), dim3(256), 0, st, n, b, d + L.lo, d + L.hi, (float4 *)(d + L.amin0), (float4 *)(d + L.amax0), per_body);
+    hipLaunchKernelGGL(k_island_box_compact, dim3((n + 255) / 256), dim3(256), 0, st, n, d + L.lo, d + L.hi, d + 1, d + L.out_label, (float *)(d + L.out_box));
+    return e;
+}
+
+// The world's query tables of shard r from local index l0 onwards (0: a shard just built; otherwise bodies [l0, nl) were appended to
+// its context). Every body is answered by one shard - the bodies whose state this shard reports (shard 0: the replicated ones too):
+// the global ids, the answer bits, and the island labels the island query reads until the context's first step. island (l0 = 0 only):
+// per GLOBAL body the label the shard is built with, or nullptr = none; an appended body is an island of its own beside the labels
+// the shard was built with.
+void upload_query_tables(edynhip_world *w, uint32_t r, uint32_t l0, const std::vector<uint32_t> *island = nullptr) {
+    Shard &s = w->shards[r];
+    const uint32_t nl = (uint32_t)s.local_ids.size(), n = w->scene.n;
+    std::vector<uint32_t> bits;
+    if (r != 0) {
+        bits.assign((size_t)nl / 32 + 1, 0u);
+        for (uint32_t l : s.owned_local) bits[l >> 5] |= 1u << (l & 31u);
+        SH_HIP(s, hipMemcpy(s.ans_dev, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (nl > l0) SH_HIP(s, hipMemcpy(s.ids_dev + l0, s.local_ids.data() + l0, (size_t)(nl - l0) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const bool labels = l0 ? s.ctx->query_island != nullptr : island && nl;
+    if (labels && nl > l0) {   // (an island lives on one shard: its label is local)
+        std::vector<uint32_t> lab(nl - l0);
+        for (uint32_t l = l0; l < nl; ++l) {
+            const uint32_t g = s.local_ids[l], root = island ? (*island)[g] : g;
+            const int32_t lr = w->rank_of[g] == (int32_t)r && root < n ? s.to_local[root] : -1;
+            lab[l - l0] = lr >= 0 ? (uint32_t)lr : l;
+        }
+        SH_HIP(s, hipMemcpy(s.qisl_dev + l0, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    shard_set_answers(s.ctx, r != 0 ? s.ans_dev : nullptr, std::move(bits), labels ? s.qisl_dev : nullptr);
+}
+
 // (Re)builds shard r for the partition w->rank_of from the scene, the current global state and what the islands carry.
 void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_state) {
     Shard &s = w->shards[r];
@@ -544,9 +468,9 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     s.local_ids.clear(); s.owned_local.clear();
     s.to_local.assign(n, -1);
     for (uint32_t i = 0; i < n; ++i)
-        if (w->rank_of[i] == (int32_t)r || w->rank_of[i] < 0) {
+        if (shard_holds_body(w->rank_of[i], r)) {
             s.to_local[i] = (int32_t)s.local_ids.size();
-            if (w->rank_of[i] == (int32_t)r || r == 0) s.owned_local.push_back((uint32_t)s.local_ids.size());   // shard 0 also reports the replicated bodies
+            if (shard_reports_body(w->rank_of[i], r)) s.owned_local.push_back((uint32_t)s.local_ids.size());
             s.local_ids.push_back(i);
         }
     const uint32_t nl = (uint32_t)s.local_ids.size();
@@ -556,11 +480,12 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
         if (!sc.jalive[g]) continue;   // removed on the running world: its index stays reserved, no context holds it any more
         const uint32_t a = sc.jbody[2 * g], b = sc.jbody[2 * g + 1];
         // a joint is an island edge: a partition that puts its two dynamic bodies on different shards is wrong - never drop it silently
-        if (w->rank_of[a] >= 0 && w->rank_of[b] >= 0 && w->rank_of[a] != w->rank_of[b]) {
+        const int32_t home = joint_home(w->rank_of[a], w->rank_of[b]);
+        if (home == -2) {
             s.rc = EDYNHIP_ERR_INTERNAL; s.err = "partition splits joint " + std::to_string(g) + " (bodies " + std::to_string(a) + ", " + std::to_string(b) + ") over two shards";
             return;
         }
-        if (s.to_local[a] >= 0 && s.to_local[b] >= 0 && (w->rank_of[a] == (int32_t)r || w->rank_of[b] == (int32_t)r)) s.local_joints.push_back(g);
+        if (home == (int32_t)r) s.local_joints.push_back(g);
     }
     edynhip_config cfg = w->cfg;
     cfg.device = s.device;
@@ -643,7 +568,7 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
         }
     }
     for (const auto &e : sc.exclusions)
-        if (s.to_local[e[0]] >= 0 && s.to_local[e[1]] >= 0 && (w->rank_of[e[0]] == (int32_t)r || w->rank_of[e[1]] == (int32_t)r))
+        if (shard_holds_exclusion(w->rank_of[e[0]], w->rank_of[e[1]], r))
             SH_TRY(s, edynhip_exclude_collision(s.ctx, (uint32_t)s.to_local[e[0]], (uint32_t)s.to_local[e[1]]));
     if (w->filter) SH_TRY(s, edynhip_set_pair_filter(s.ctx, &shard_filter_thunk, &w->shard_filters[r]));
     if (carry.any) {
@@ -713,26 +638,8 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     }
     SH_HIP(s, hipMemset(s.mon_dev, 0, words * sizeof(uint32_t)));
     // queries: every body is answered by one shard - the bodies whose state this shard reports (shard 0: the replicated ones too)
-    {
-        std::vector<uint32_t> bits;
-        if (r != 0) {
-            bits.assign((size_t)nl / 32 + 1, 0u);
-            for (uint32_t l : s.owned_local) bits[l >> 5] |= 1u << (l & 31u);
-            SH_HIP(s, hipMemcpy(s.ans_dev, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-        if (nl) SH_HIP(s, hipMemcpy(s.ids_dev, s.local_ids.data(), (size_t)nl * sizeof(uint32_t), hipMemcpyHostToDevice));
-        const bool labels = carry.any && carry.island.size() == n && nl;
-        if (labels) {   // (an island lives on one shard: its label is local)
-            std::vector<uint32_t> lab(nl);
-            for (uint32_t l = 0; l < nl; ++l) {
-                const uint32_t g = s.local_ids[l], root = carry.island[g];
-                const int32_t lr = w->rank_of[g] == (int32_t)r && root < n ? s.to_local[root] : -1;
-                lab[l] = lr >= 0 ? (uint32_t)lr : l;
-            }
-            SH_HIP(s, hipMemcpy(s.qisl_dev, lab.data(), (size_t)nl * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-        shard_set_answers(s.ctx, r != 0 ? s.ans_dev : nullptr, std::move(bits), labels ? s.qisl_dev : nullptr);
-    }
+    upload_query_tables(w, r, 0, carry.any && carry.island.size() == n ? &carry.island : nullptr);
+    if (s.rc != EDYNHIP_OK) return;
     trace.mark("warm start, sleep state, gather / monitor buffers");
 }
 
@@ -825,10 +732,7 @@ void island_boxes_shard(edynhip_world *w, uint32_t r, bool per_body) {
     hipStream_t st = s.ctx->stream;
     const MonLayout L(s.cap);
     uint32_t *d = s.mon_dev;
-    SH_HIP(s, hipMemsetAsync(d, 0, 2 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_island_box_clear, dim3((3 * nl + 255) / 256), dim3(256), 0, st, nl, d + L.lo, d + L.hi);
-    hipLaunchKernelGGL(k_island_box_reduce, dim3((nl + 255) / 256), dim3(256), 0, st, nl, s.ctx->b, d + L.lo, d + L.hi, (float4 *)(d + L.amin0), (float4 *)(d + L.amax0), per_body);
-    hipLaunchKernelGGL(k_island_box_compact, dim3((nl + 255) / 256), dim3(256), 0, st, nl, d + L.lo, d + L.hi, d + 1, d + L.out_label, (float *)(d + L.out_box));
+    SH_HIP(s, launch_island_boxes(st, nl, s.ctx->b, d, L, per_body));
     SH_HIP(s, hipMemcpyAsync(s.mon_host, d, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SH_HIP(s, hipStreamSynchronize(st));
     const uint32_t k = s.mon_host[1];
@@ -862,11 +766,8 @@ int approach_check(edynhip_world *w, bool &close, bool per_body = false, const s
             boxes.push_back(b);
         }
     }
-    float gmin = kHorizon;
-    sweep_boxes(boxes, 0.5f * kHorizon, true, [&](const IslandBox &, const IslandBox &, float gap) { gmin = std::min(gmin, gap); });
     ++w->stats.approach_checks;
-    close = !(gmin >= 2 * kCreationMargin);   // also true for NaN
-    w->budget = close ? 0.0f : gmin - 2 * kCreationMargin;
+    approach_verdict(boxes, close, w->budget);
     return EDYNHIP_OK;
 }
 
@@ -910,12 +811,6 @@ void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy) {
     }
 }
 
-inline uint64_t canonical_key(const HostScene &sc, uint32_t a, uint32_t b) {   // (owner << 32) | other: the owner is the dynamic body, the higher index of two
-    const bool da = sc.kind[a] == EDYNHIP_KIND_DYNAMIC, db = sc.kind[b] == EDYNHIP_KIND_DYNAMIC;
-    const uint32_t owner = (da && db) ? std::max(a, b) : (da ? a : b), other = owner == a ? b : a;
-    return ((uint64_t)owner << 32) | other;
-}
-
 // gathers the manifolds of all shards, each once, global indices, canonical order; ids (or nullptr): their points' ids [m][4], in that order
 void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::vector<uint64_t> *ids = nullptr) {
     out.clear();
@@ -932,7 +827,7 @@ void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::
     // canonical order: sort (key, position) pairs and move every 336-byte record once (a stable sort of the records themselves, with
     // the key recomputed in every comparison, was 0.15-0.3 s of a re-partition)
     std::vector<std::pair<uint64_t, uint32_t>> order(out.size());
-    for (uint32_t k = 0; k < out.size(); ++k) order[k] = {canonical_key(w->scene, out[k].body[0], out[k].body[1]), k};
+    for (uint32_t k = 0; k < out.size(); ++k) order[k] = {canonical_key(w->scene.kind.data(), out[k].body[0], out[k].body[1]), k};
     std::sort(order.begin(), order.end());   // (ties keep their gathering order: the position is the second key)
     std::vector<edynhip_manifold> sorted(out.size());
     for (uint32_t k = 0; k < out.size(); ++k) sorted[k] = out[order[k].second];
@@ -954,6 +849,15 @@ void carry_point_ids(const Shard &s, Carry &carry) {
     }
 }
 
+// the applied impulses and tracked angles of a collected shard's joints go with the re-partition, by global joint
+void carry_joint_impulses(const Shard &s, Carry &carry) {
+    for (uint32_t lj = 0; lj < s.local_joints.size() && !s.imp24.empty(); ++lj) {
+        const uint32_t g = s.local_joints[lj];
+        std::memcpy(&carry.imp24[(size_t)g * 24], &s.imp24[(size_t)lj * 24], 24 * sizeof(float));
+        carry.angle[g] = s.imp10[(size_t)lj * 10 + 9];
+    }
+}
+
 // `only` (or nullptr = all): the shards to build; the others keep their contexts - their bodies, and therefore their local indices, are unchanged.
 int rebuild(edynhip_world *w, const Carry &carry, bool from_state, const std::vector<uint8_t> *only = nullptr) {
     PhaseTrace trace(w, "rebuild");
@@ -963,7 +867,7 @@ int rebuild(edynhip_world *w, const Carry &carry, bool from_state, const std::ve
     w->pool->run([w](uint32_t r) { gather_shard(w, r, false); });
     EH_TRY(shard_error(w));
     trace.mark("gather");
-    for (uint32_t r = 0; r < w->shards.size(); ++r) w->stats.bodies_per_shard[r < 16 ? r : 15] = (uint32_t)w->shards[r].owned_local.size();
+    refresh_bodies_per_shard(w);
     w->built = true;
     bool close = false;
     // a fresh partition keeps close islands together: the check sets the budget and records the reference boxes the growth is measured against
@@ -1042,52 +946,19 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
                 if (w->rank_of[a] == (int32_t)r) weights[a] += m.num_points;
                 if (w->rank_of[b] == (int32_t)r) weights[b] += m.num_points;
             }
-            for (uint32_t lj = 0; lj < s.local_joints.size() && !s.imp24.empty(); ++lj) {
-                const uint32_t g = s.local_joints[lj];
-                std::memcpy(&carry.imp24[(size_t)g * 24], &s.imp24[(size_t)lj * 24], 24 * sizeof(float));
-                carry.angle[g] = s.imp10[(size_t)lj * 10 + 9];
-            }
+            carry_joint_impulses(s, carry);
         }
         merge_manifolds(w, carry.manifolds);
     };
     if (!sticky) take_heavy(nullptr);
-    // islands whose boxes overlap (grown by the creation margin) must end up on one shard: weld them - all such pairs, also those the
-    // last partition had co-located (they may still be separate islands, and the partitioner would be free to split them)
+    // The islands that must end up on one shard, welded (weld_islands): overlapping boxes, live joints, the edit's edges, carried
+    // manifolds. (A sticky re-partition follows a step of every shard: labels are current, and it carries no manifold list.)
     std::vector<IslandBox> boxes;
-    {
-        std::vector<uint32_t> isl;
-        for (uint32_t i = 0; i < n; ++i) if (sc.kind[i] == EDYNHIP_KIND_DYNAMIC) isl.push_back(labels[i]);
-        std::sort(isl.begin(), isl.end()); isl.erase(std::unique(isl.begin(), isl.end()), isl.end());
-        boxes.resize(isl.size());
-        for (size_t k = 0; k < isl.size(); ++k) { for (int d = 0; d < 3; ++d) { boxes[k].lo[d] = 3.0e38f; boxes[k].hi[d] = -3.0e38f; } boxes[k].label = isl[k]; boxes[k].owner = 0; }
-        for (uint32_t i = 0; i < n; ++i) {
-            if (sc.kind[i] != EDYNHIP_KIND_DYNAMIC || sc.shape_type[i] == EDYNHIP_SHAPE_NONE) continue;   // a shapeless body touches nothing
-            IslandBox &b = boxes[std::lower_bound(isl.begin(), isl.end(), labels[i]) - isl.begin()];
-            for (int d = 0; d < 3; ++d) { b.lo[d] = std::min(b.lo[d], aabb[6 * (size_t)i + d]); b.hi[d] = std::max(b.hi[d], aabb[6 * (size_t)i + 3 + d]); }
-        }
-    }
-    std::vector<uint32_t> parent(n);
-    std::iota(parent.begin(), parent.end(), 0u);
-    auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
-    // The device labels are those of the shards' LAST island stage: a shard that has not stepped since it was built (a re-partition
-    // before the first step, or right after a step that re-partitioned by itself) still has the labels it was built with. The edges the
-    // island manager connects bodies through are known on the host - every joint and every carried manifold between two dynamic bodies
-    // (island_manager.cpp:117-247) - so they are united here, whatever the labels say: cheap, and a joint or a carried manifold can
-    // never end up with its bodies on two shards. (A sticky re-partition follows a step of every shard: labels are current.)
-    auto unite = [&](uint32_t a, uint32_t b) {
-        if (sc.kind[a] != EDYNHIP_KIND_DYNAMIC || sc.kind[b] != EDYNHIP_KIND_DYNAMIC) return;
-        const uint32_t ra = find(labels[a]), rb = find(labels[b]);
-        if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
-    };
-    for (uint32_t g = 0; g < sc.nj; ++g) if (sc.jalive[g]) unite(sc.jbody[2 * g], sc.jbody[2 * g + 1]);
-    if (edges) for (const auto &e : *edges) unite(e[0], e[1]);
-    for (const edynhip_manifold &m : carry.manifolds) unite(m.body[0], m.body[1]);
-    sweep_boxes(boxes, kCreationMargin, false, [&](const IslandBox &a, const IslandBox &b, float) {
-        const uint32_t ra = find(a.label), rb = find(b.label);
-        if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
-    });
-    std::vector<uint32_t> welded(n);
-    for (uint32_t i = 0; i < n; ++i) welded[i] = find(labels[i]);
+    std::vector<EdgeSpan> tied;
+    if (sc.nj) tied.push_back({sc.jbody.data(), 2 * sizeof(uint32_t), sc.nj, sc.jalive.data()});
+    if (edges && !edges->empty()) tied.push_back({edges->data(), sizeof((*edges)[0]), edges->size(), nullptr});
+    if (!carry.manifolds.empty()) tied.push_back({carry.manifolds[0].body, sizeof(edynhip_manifold), carry.manifolds.size(), nullptr});
+    const std::vector<uint32_t> welded = weld_islands(n, labels.data(), sc.kind.data(), sc.shape_type.data(), aabb.data(), tied, boxes);
     ++w->stats.repartitions;
     trace.mark("island boxes, welding");
     if (!sticky) {
@@ -1095,35 +966,10 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
         partition_islands_spatial(n, welded.data(), sc.kind.data(), weights.data(), aabb.data(), W, w->rank_of.data());
         return rebuild(w, carry, true);
     }
-    // sticky: a group that spans shards goes to the shard holding most of its bodies (ties: the lower shard); everybody else stays
-    std::vector<int32_t> next = w->rank_of;
-    {
-        std::vector<uint32_t> order;
-        for (uint32_t i = 0; i < n; ++i) if (sc.kind[i] == EDYNHIP_KIND_DYNAMIC) order.push_back(i);
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return welded[a] != welded[b] ? welded[a] < welded[b] : a < b; });
-        std::vector<uint32_t> count(W);
-        for (size_t a = 0; a < order.size();) {
-            size_t e = a;
-            std::fill(count.begin(), count.end(), 0u);
-            while (e < order.size() && welded[order[e]] == welded[order[a]]) { ++count[(uint32_t)w->rank_of[order[e]]]; ++e; }
-            uint32_t target = 0, spans = 0;
-            for (uint32_t r = 0; r < W; ++r) { if (count[r]) ++spans; if (count[r] > count[target]) target = r; }
-            if (spans > 1) for (size_t k = a; k < e; ++k) next[order[k]] = (int32_t)target;
-            a = e;
-        }
-    }
-    // Sticky moves only ever add to the shard that holds most of a group: a collapsing or merging scene would drift onto a few shards.
-    // Once the heaviest shard carries more than 1.5 x the mean, this meeting takes the full, spatially balanced re-partition instead
-    // (the price is one rebuild of every shard, the gain every later step of the slowest shard).
-    if (W > 1) {
-        std::vector<uint32_t> load(W, 0);
-        uint32_t total = 0;
-        for (uint32_t i = 0; i < n; ++i) if (next[i] >= 0) { ++load[(uint32_t)next[i]]; ++total; }
-        const uint32_t heaviest = *std::max_element(load.begin(), load.end());
-        if (total >= 8 * W && (double)heaviest * W > 1.5 * (double)total) {
-            ++w->stats.rebalances; --w->stats.repartitions;   // (counted again by the full pass)
-            return repartition(w, false, edges, nullptr, from_edit);
-        }
+    const std::vector<int32_t> next = sticky_targets(n, welded.data(), sc.kind.data(), w->rank_of.data(), W);
+    if (needs_rebalance(n, next.data(), W)) {   // this meeting takes the full, spatially balanced re-partition instead
+        ++w->stats.rebalances; --w->stats.repartitions;   // (counted again by the full pass)
+        return repartition(w, false, edges, nullptr, from_edit);
     }
     std::vector<uint8_t> changed(W, 0);
     for (uint32_t i = 0; i < n; ++i) if (next[i] != w->rank_of[i]) { changed[(uint32_t)next[i]] = 1; changed[(uint32_t)w->rank_of[i]] = 1; }
@@ -1138,17 +984,7 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
     w->pool->run([w, &changed](uint32_t r) { if (changed[r]) collect_shard(w, r, false, true); });
     EH_TRY(shard_error(w));
     trace.mark("collect manifolds / joint impulses of the changed shards");
-    for (uint32_t r = 0; r < W; ++r) if (changed[r]) carry_point_ids(w->shards[r], carry);
-    // joints' applied impulses and angles of the changed shards
-    for (uint32_t r = 0; r < W; ++r) {
-        Shard &s = w->shards[r];
-        if (!changed[r]) continue;
-        for (uint32_t lj = 0; lj < s.local_joints.size() && !s.imp24.empty(); ++lj) {
-            const uint32_t g = s.local_joints[lj];
-            std::memcpy(&carry.imp24[(size_t)g * 24], &s.imp24[(size_t)lj * 24], 24 * sizeof(float));
-            carry.angle[g] = s.imp10[(size_t)lj * 10 + 9];
-        }
-    }
+    for (uint32_t r = 0; r < W; ++r) if (changed[r]) { carry_point_ids(w->shards[r], carry); carry_joint_impulses(w->shards[r], carry); }
     // Manifolds: a body that stays in its shard keeps its place among the others that stay (local indices ascend with the global ones), so
     // the manifolds that stay ARE in canonical order already; only those whose island moves are taken out, sorted among themselves and
     // merged into their new shard's list. No global sort, one copy per record at most (the merged, sorted list of every changed shard's
@@ -1177,7 +1013,7 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
     w->pool->run([&](uint32_t r) {
         if (!changed[r]) return;
         Shard &s = w->shards[r];
-        auto key_less = [&](const edynhip_manifold &x, const edynhip_manifold &y) { return canonical_key(sc, x.body[0], x.body[1]) < canonical_key(sc, y.body[0], y.body[1]); };
+        auto key_less = [&](const edynhip_manifold &x, const edynhip_manifold &y) { return canonical_key(sc.kind.data(), x.body[0], x.body[1]) < canonical_key(sc.kind.data(), y.body[0], y.body[1]); };
         if (incoming[r].empty()) { carry.per_shard[r].swap(s.manifolds); return; }
         std::sort(incoming[r].begin(), incoming[r].end(), key_less);
         carry.per_shard[r].resize(s.manifolds.size() + incoming[r].size());
@@ -1192,6 +1028,13 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
     return rc_rebuild;
 }
 
+// the scene's meshes as the island estimate reads them
+MeshRadii scene_meshes(const HostScene &sc) {
+    MeshRadii m;
+    for (const HostScene::Mesh &mesh : sc.meshes) m.add(mesh.v.data(), mesh.v.size() / 3);
+    return m;
+}
+
 int ensure_built(edynhip_world *w) {
     if (w->built) return EDYNHIP_OK;
     const HostScene &sc = w->scene;
@@ -1199,57 +1042,12 @@ int ensure_built(edynhip_world *w) {
     if (n == 0) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world: no bodies");
     // The islands of the initial state, estimated on the HOST (round 6; until round 5 a probe context on devices[0] held the WHOLE scene and
     // ran broadphase, narrowphase and the island stage - a sharded scene had to fit one GPU, and a quarter-million-body probe cost seconds).
-    // An island edge exists once a manifold exists (constraint_util.cpp:76-78: every manifold owns a null_constraint edge), i.e. once two
-    // AABBs come within the creation margin (broadphase.hpp:15-18), or through a joint (island_manager.cpp:117-247). The partition only
-    // has to keep every TRUE island on one shard, so a conservative edge set is as good as the exact one - it merely co-locates islands
-    // that are about to meet anyway: every dynamic shaped body gets the box of its bounding sphere (no collision filters, no exclusions
-    // applied), boxes within the margin and jointed bodies are united, the label of a component is its lowest body index, as on the device.
+    // The partition only has to keep every true island on one shard: estimate_islands (bounding-sphere boxes within the creation margin, joints).
     std::vector<uint32_t> labels(n);
     std::vector<float> aabb0((size_t)n * 6, 0.f);
-    {
-        std::vector<float> mesh_radius(sc.meshes.size(), 0.f);
-        for (size_t k = 0; k < sc.meshes.size(); ++k) {
-            const std::vector<float> &v = sc.meshes[k].v;
-            double c[3] = {0, 0, 0};
-            const size_t nv = v.size() / 3;
-            for (size_t i = 0; i < nv; ++i) for (int d = 0; d < 3; ++d) c[d] += v[3 * i + d];
-            for (int d = 0; d < 3; ++d) c[d] /= (double)std::max<size_t>(nv, 1);
-            double r2 = 0;
-            for (size_t i = 0; i < nv; ++i) { double q = 0; for (int d = 0; d < 3; ++d) q += (v[3 * i + d] - c[d]) * (v[3 * i + d] - c[d]); r2 = std::max(r2, q); }
-            mesh_radius[k] = 2.0f * (float)std::sqrt(r2);   // (the centroid the library shifts to lies inside the hull: twice the radius about the mean covers it)
-        }
-        std::vector<IslandBox> boxes;
-        for (uint32_t i = 0; i < n; ++i) {
-            if (sc.kind[i] != EDYNHIP_KIND_DYNAMIC) continue;
-            const float *p = &sc.shape_param[4 * (size_t)i];
-            float r = -1.0f;
-            switch (sc.shape_type[i]) {
-            case EDYNHIP_SHAPE_BOX: r = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]); break;
-            case EDYNHIP_SHAPE_SPHERE: r = p[0]; break;
-            case EDYNHIP_SHAPE_CAPSULE: r = p[0] + p[1]; break;
-            case EDYNHIP_SHAPE_CYLINDER: r = std::sqrt(p[0] * p[0] + p[1] * p[1]); break;
-            case EDYNHIP_SHAPE_POLYHEDRON: { const size_t id = (size_t)p[0]; r = id < mesh_radius.size() ? mesh_radius[id] : 0.0f; break; }
-            default: break;   // no shape (or a plane, which is never dynamic in a sensible scene): touches nothing
-            }
-            if (r < 0) continue;
-            if (!sc.com.empty()) r += std::sqrt(sc.com[3 * (size_t)i] * sc.com[3 * (size_t)i] + sc.com[3 * (size_t)i + 1] * sc.com[3 * (size_t)i + 1] + sc.com[3 * (size_t)i + 2] * sc.com[3 * (size_t)i + 2]);
-            IslandBox b;
-            for (int d = 0; d < 3; ++d) { b.lo[d] = sc.pos[3 * (size_t)i + d] - r; b.hi[d] = sc.pos[3 * (size_t)i + d] + r; aabb0[6 * (size_t)i + d] = b.lo[d]; aabb0[6 * (size_t)i + 3 + d] = b.hi[d]; }
-            b.label = i; b.owner = 0;
-            boxes.push_back(b);
-        }
-        std::vector<uint32_t> parent(n);
-        std::iota(parent.begin(), parent.end(), 0u);
-        auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
-        auto unite = [&](uint32_t a, uint32_t b) { const uint32_t ra = find(a), rb = find(b); if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb); };
-        sweep_boxes(boxes, kCreationMargin, false, [&](const IslandBox &a, const IslandBox &b, float) { unite(a.label, b.label); });
-        for (uint32_t g = 0; g < sc.nj; ++g) {
-            if (!sc.jalive[g]) continue;
-            const uint32_t a = sc.jbody[2 * g], b = sc.jbody[2 * g + 1];
-            if (sc.kind[a] == EDYNHIP_KIND_DYNAMIC && sc.kind[b] == EDYNHIP_KIND_DYNAMIC) unite(a, b);
-        }
-        for (uint32_t i = 0; i < n; ++i) labels[i] = find(i);
-    }
+    MeshRadii meshes = scene_meshes(sc);
+    estimate_islands({n, sc.kind.data(), sc.shape_type.data(), sc.shape_param.data(), sc.pos.data(), data_or_null(sc.com)}, meshes, sc.nj, sc.jbody.data(), sc.jalive.data(),
+                     labels.data(), aabb0.data());
     w->rank_of.assign(n, -1);
     partition_islands_spatial(n, labels.data(), sc.kind.data(), nullptr, aabb0.data(), W, w->rank_of.data());
     w->pos = sc.pos; w->orn = sc.orn; w->linvel = sc.linvel; w->angvel = sc.angvel;
@@ -1257,7 +1055,59 @@ int ensure_built(edynhip_world *w) {
     return rebuild(w, none, false);
 }
 
-template <typename T> void copy_in(std::vector<T> &dst, const T *src, size_t count) { if (src) dst.assign(src, src + count); else dst.clear(); }
+// k bodies as they are described appended to the scene (onto an empty scene: edynhip_world_set_bodies)
+void scene_append_bodies(edynhip_world *w, uint32_t k, const edynhip_bodies *in) {
+    HostScene &sc = w->scene;
+    const size_t n0 = sc.n;
+    auto app = [&](auto &vec, const auto *src, size_t width) { vec.insert(vec.end(), src, src + (size_t)k * width); };
+    // an optional array the scene or the new bodies lack reads as its default there
+    auto opt = [&](auto &vec, const auto *src, size_t width, const auto *def_row) {
+        if (vec.empty() && !src) return;
+        if (vec.empty()) { vec.resize(n0 * width); for (size_t i = 0; i < vec.size(); ++i) vec[i] = def_row[i % width]; }
+        if (src) vec.insert(vec.end(), src, src + (size_t)k * width);
+        else for (size_t i = 0; i < (size_t)k * width; ++i) vec.push_back(def_row[i % width]);
+    };
+    app(sc.kind, in->kind, 1); app(sc.shape_type, in->shape_type, 1);
+    app(sc.pos, in->pos, 3); app(sc.orn, in->orn, 4); app(sc.linvel, in->linvel, 3); app(sc.angvel, in->angvel, 3);
+    app(sc.mass, in->mass, 1); app(sc.shape_param, in->shape_param, 4); app(sc.friction, in->friction, 1); app(sc.restitution, in->restitution, 1);
+    const bool own_inertia = in->inertia && in->has_inertia;
+    const float zeros[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const uint8_t zero8 = 0;
+    const uint64_t all = ~0ull;
+    opt(sc.inertia, own_inertia ? in->inertia : (const float *)nullptr, 9, zeros);
+    opt(sc.has_inertia, own_inertia ? in->has_inertia : (const uint8_t *)nullptr, 1, &zero8);
+    opt(sc.group, in->group, 1, &all); opt(sc.mask, in->mask, 1, &all);
+    opt(sc.gravity, in->gravity, 3, w->cfg.gravity);
+    opt(sc.sleeping_disabled, in->sleeping_disabled, 1, &zero8);
+    opt(sc.com, in->center_of_mass, 3, zeros);
+    sc.n += k;
+    w->removed.resize(sc.n, 0);
+    w->stats.num_bodies = sc.n;
+}
+
+// n joints appended to the scene, alive (onto a scene without joints: edynhip_world_set_joints)
+void scene_append_joints(HostScene &sc, uint32_t n, const edynhip_joints *in) {
+    if (n == 0) return;
+    sc.jtype.insert(sc.jtype.end(), in->type, in->type + n); sc.jbody.insert(sc.jbody.end(), in->body, in->body + 2 * (size_t)n);
+    sc.jpivot.insert(sc.jpivot.end(), in->pivot, in->pivot + 6 * (size_t)n);
+    if (in->axis) sc.jaxis.insert(sc.jaxis.end(), in->axis, in->axis + 6 * (size_t)n); else sc.jaxis.resize(sc.jaxis.size() + 6 * (size_t)n, 0.f);
+    if (in->params) sc.jparams.insert(sc.jparams.end(), in->params, in->params + 10 * (size_t)n); else sc.jparams.resize(sc.jparams.size() + 10 * (size_t)n, 0.f);
+    sc.nj += n;
+    sc.jalive.resize(sc.nj, 1);
+}
+
+HostScene::Def make_def(uint32_t joint, const float *frame_a9, const float *frame_b9, const float *params, bool generic) {
+    HostScene::Def d;
+    d.joint = joint; d.generic = generic;
+    d.fa.assign(frame_a9, frame_a9 + 9); d.fb.assign(frame_b9, frame_b9 + 9); d.p.assign(params, params + (generic ? 60 : 16));
+    return d;
+}
+
+// the removed bodies' manifolds are gone (a step dropped them, or no context ever held them): their slots are shapeless static bodies from here on
+void finish_tombstones(edynhip_world *w) {
+    for (uint32_t g : w->pending_tombs) { w->scene.kind[g] = EDYNHIP_KIND_STATIC; w->scene.shape_type[g] = EDYNHIP_SHAPE_NONE; }
+    w->pending_tombs.clear();
+}
 
 }  // namespace
 
@@ -1300,10 +1150,7 @@ int edynhip_get_island_boxes(edynhip_ctx *c, uint32_t *labels, float *boxes6, ui
     EH_HIP(c, hipMalloc((void **)&d, L.words * sizeof(uint32_t)));
     uint32_t *count = d + 1, *out_label = d + L.out_label;
     float *out_box = (float *)(d + L.out_box);
-    hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(uint32_t), c->stream);
-    hipLaunchKernelGGL(k_island_box_clear, dim3((3 * n + 255) / 256), dim3(256), 0, c->stream, n, d + L.lo, d + L.hi);
-    hipLaunchKernelGGL(k_island_box_reduce, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->b, d + L.lo, d + L.hi, (float4 *)(d + L.amin0), (float4 *)(d + L.amax0), false);
-    hipLaunchKernelGGL(k_island_box_compact, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d + L.lo, d + L.hi, count, out_label, out_box);
+    hipError_t e = launch_island_boxes(c->stream, n, c->b, d, L, false);
     uint32_t k = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&k, count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1381,13 +1228,11 @@ int edynhip_world_set_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies 
     if (!in->kind || !in->pos || !in->orn || !in->linvel || !in->angvel || !in->mass || !in->shape_type || !in->shape_param || !in->friction || !in->restitution)
         return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_set_bodies: missing array");
     HostScene &sc = w->scene;
-    sc.n = n;
-    copy_in(sc.kind, in->kind, n); copy_in(sc.shape_type, in->shape_type, n);
-    copy_in(sc.pos, in->pos, 3 * (size_t)n); copy_in(sc.orn, in->orn, 4 * (size_t)n); copy_in(sc.linvel, in->linvel, 3 * (size_t)n); copy_in(sc.angvel, in->angvel, 3 * (size_t)n);
-    copy_in(sc.mass, in->mass, n); copy_in(sc.shape_param, in->shape_param, 4 * (size_t)n); copy_in(sc.friction, in->friction, n); copy_in(sc.restitution, in->restitution, n);
-    copy_in(sc.inertia, in->has_inertia ? in->inertia : nullptr, 9 * (size_t)n); copy_in(sc.has_inertia, in->inertia ? in->has_inertia : nullptr, n);
-    copy_in(sc.group, in->group, n); copy_in(sc.mask, in->mask, n); copy_in(sc.gravity, in->gravity, 3 * (size_t)n);
-    copy_in(sc.sleeping_disabled, in->sleeping_disabled, n); copy_in(sc.com, in->center_of_mass, 3 * (size_t)n);
+    sc.n = 0;
+    sc.kind.clear(); sc.shape_type.clear(); sc.pos.clear(); sc.orn.clear(); sc.linvel.clear(); sc.angvel.clear(); sc.mass.clear(); sc.shape_param.clear();
+    sc.friction.clear(); sc.restitution.clear(); sc.inertia.clear(); sc.has_inertia.clear(); sc.group.clear(); sc.mask.clear(); sc.gravity.clear();
+    sc.sleeping_disabled.clear(); sc.com.clear();
+    scene_append_bodies(w, n, in);
     sc.nj = 0; sc.jtype.clear(); sc.jbody.clear(); sc.jpivot.clear(); sc.jaxis.clear(); sc.jparams.clear(); sc.jalive.clear(); sc.defs.clear(); sc.exclusions.clear();
     w->removed.assign(n, 0); w->pending_tombs.clear();
     w->built = false; w->stepped = false;
@@ -1405,11 +1250,8 @@ int edynhip_world_set_joints(edynhip_world *w, uint32_t n, const edynhip_joints 
     if (w->stepped) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_set_joints: the world has been stepped; describe the scene again (edynhip_world_set_bodies with the current state) before editing it");
     HostScene &sc = w->scene;
     for (uint32_t k = 0; k < 2 * n; ++k) if (in->body[k] >= sc.n) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_set_joints: body index out of range");
-    sc.nj = n;
-    copy_in(sc.jtype, n ? in->type : nullptr, n); copy_in(sc.jbody, n ? in->body : nullptr, 2 * (size_t)n); copy_in(sc.jpivot, n ? in->pivot : nullptr, 6 * (size_t)n);
-    if (n && in->axis) copy_in(sc.jaxis, in->axis, 6 * (size_t)n); else sc.jaxis.assign(6 * (size_t)n, 0.f);
-    if (n && in->params) copy_in(sc.jparams, in->params, 10 * (size_t)n); else sc.jparams.assign(10 * (size_t)n, 0.f);
-    sc.jalive.assign(n, 1);
+    sc.nj = 0; sc.jtype.clear(); sc.jbody.clear(); sc.jpivot.clear(); sc.jaxis.clear(); sc.jparams.clear(); sc.jalive.clear();
+    scene_append_joints(sc, n, in);
     sc.defs.clear();
     w->built = false;
     return EDYNHIP_OK;
@@ -1418,10 +1260,7 @@ int edynhip_world_set_joints(edynhip_world *w, uint32_t n, const edynhip_joints 
 int edynhip_world_set_joint_definition(edynhip_world *w, uint32_t joint, const float *frame_a9, const float *frame_b9, const float *params, int generic) {
     if (!w || !frame_a9 || !frame_b9 || !params || joint >= w->scene.nj) return EDYNHIP_ERR_INVALID;
     if (w->stepped) return w->fail(EDYNHIP_ERR_UNSUPPORTED, "edynhip_world_set_joint_definition: the world has been stepped; describe the scene again first (see edynhip_world_set_joints)");
-    HostScene::Def d;
-    d.joint = joint; d.generic = generic != 0;
-    d.fa.assign(frame_a9, frame_a9 + 9); d.fb.assign(frame_b9, frame_b9 + 9); d.p.assign(params, params + (generic ? 60 : 16));
-    w->scene.defs.push_back(std::move(d));
+    w->scene.defs.push_back(make_def(joint, frame_a9, frame_b9, params, generic != 0));
     w->built = false;
     return EDYNHIP_OK;
 }
@@ -1475,10 +1314,7 @@ int edynhip_world_step(edynhip_world *w, uint32_t nsteps) {
         EH_TRY(shard_error(w));
         ++w->stats.steps; ++w->step_count;
         w->stepped = true;
-        if (!w->pending_tombs.empty()) {   // the step dropped the removed bodies' manifolds: their slots are shapeless static bodies from here on
-            for (uint32_t g : w->pending_tombs) { w->scene.kind[g] = EDYNHIP_KIND_STATIC; w->scene.shape_type[g] = EDYNHIP_SHAPE_NONE; }
-            w->pending_tombs.clear();
-        }
+        finish_tombstones(w);   // the step dropped the removed bodies' manifolds
         if (events) EH_TRY(append_events(w));
         if (w->shards.size() < 2) continue;
         float growth = 0.0f;
@@ -1600,40 +1436,6 @@ edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard) {
 // The global-to-local maps stay ascending because a new body or joint has the highest global AND the highest local index.
 namespace {
 
-void scene_append_bodies(edynhip_world *w, uint32_t k, const edynhip_bodies *in) {
-    HostScene &sc = w->scene;
-    const size_t n0 = sc.n;
-    auto app = [&](auto &vec, const auto *src, size_t width) { vec.insert(vec.end(), src, src + (size_t)k * width); };
-    // an optional array the scene or the new bodies lack reads as its default there
-    auto opt = [&](auto &vec, const auto *src, size_t width, const auto *def_row) {
-        if (vec.empty() && !src) return;
-        if (vec.empty()) { vec.resize(n0 * width); for (size_t i = 0; i < vec.size(); ++i) vec[i] = def_row[i % width]; }
-        if (src) vec.insert(vec.end(), src, src + (size_t)k * width);
-        else for (size_t i = 0; i < (size_t)k * width; ++i) vec.push_back(def_row[i % width]);
-    };
-    app(sc.kind, in->kind, 1); app(sc.shape_type, in->shape_type, 1);
-    app(sc.pos, in->pos, 3); app(sc.orn, in->orn, 4); app(sc.linvel, in->linvel, 3); app(sc.angvel, in->angvel, 3);
-    app(sc.mass, in->mass, 1); app(sc.shape_param, in->shape_param, 4); app(sc.friction, in->friction, 1); app(sc.restitution, in->restitution, 1);
-    const bool own_inertia = in->inertia && in->has_inertia;
-    const float zeros[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const uint8_t zero8 = 0;
-    const uint64_t all = ~0ull;
-    opt(sc.inertia, own_inertia ? in->inertia : (const float *)nullptr, 9, zeros);
-    opt(sc.has_inertia, own_inertia ? in->has_inertia : (const uint8_t *)nullptr, 1, &zero8);
-    opt(sc.group, in->group, 1, &all); opt(sc.mask, in->mask, 1, &all);
-    opt(sc.gravity, in->gravity, 3, w->cfg.gravity);
-    opt(sc.sleeping_disabled, in->sleeping_disabled, 1, &zero8);
-    opt(sc.com, in->center_of_mass, 3, zeros);
-    sc.n += k;
-    w->removed.resize(sc.n, 0);
-    w->stats.num_bodies = sc.n;
-}
-
-void finish_tombstones(edynhip_world *w) {
-    for (uint32_t g : w->pending_tombs) { w->scene.kind[g] = EDYNHIP_KIND_STATIC; w->scene.shape_type[g] = EDYNHIP_SHAPE_NONE; }
-    w->pending_tombs.clear();
-}
-
 void scene_tombstones(edynhip_world *w, const std::vector<uint32_t> &gone) {
     HostScene &sc = w->scene;
     // A context keeps a removed body's manifolds until its next step drops them (with their destroy events). Until then the scene keeps
@@ -1647,32 +1449,6 @@ void scene_tombstones(edynhip_world *w, const std::vector<uint32_t> &gone) {
                         sc.exclusions.end());
 }
 
-// radius of a sphere about the body's position that holds its shape (ensure_built's estimate); negative: no shape, touches nothing
-float bounding_radius(const HostScene &sc, int shape_type, const float *p, const float *com) {
-    float r = -1.0f;
-    switch (shape_type) {
-    case EDYNHIP_SHAPE_BOX: r = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]); break;
-    case EDYNHIP_SHAPE_SPHERE: r = p[0]; break;
-    case EDYNHIP_SHAPE_CAPSULE: r = p[0] + p[1]; break;
-    case EDYNHIP_SHAPE_CYLINDER: r = std::sqrt(p[0] * p[0] + p[1] * p[1]); break;
-    case EDYNHIP_SHAPE_POLYHEDRON: {
-        const size_t id = (size_t)p[0];
-        if (id >= sc.meshes.size()) return 0.0f;
-        const std::vector<float> &v = sc.meshes[id].v;
-        double c[3] = {0, 0, 0}, r2 = 0;
-        const size_t nv = v.size() / 3;
-        for (size_t i = 0; i < nv; ++i) for (int d = 0; d < 3; ++d) c[d] += v[3 * i + d];
-        for (int d = 0; d < 3; ++d) c[d] /= (double)std::max<size_t>(nv, 1);
-        for (size_t i = 0; i < nv; ++i) { double q = 0; for (int d = 0; d < 3; ++d) q += (v[3 * i + d] - c[d]) * (v[3 * i + d] - c[d]); r2 = std::max(r2, q); }
-        r = 2.0f * (float)std::sqrt(r2);
-        break;
-    }
-    default: return -1.0f;
-    }
-    if (com) r += std::sqrt(com[0] * com[0] + com[1] * com[1] + com[2] * com[2]);
-    return r;
-}
-
 // the shard that holds global joint j in its context (-1: none - a removed joint, or one between two replicated bodies) and its index there
 int32_t joint_shard(const edynhip_world *w, uint32_t j, uint32_t &local) {
     for (uint32_t r = 0; r < w->shards.size(); ++r) {
@@ -1683,11 +1459,9 @@ int32_t joint_shard(const edynhip_world *w, uint32_t j, uint32_t &local) {
     return -1;
 }
 
-// the shard a joint between global bodies a and b lives on by build_shard's rule (-1: both replicated - no context holds it; -2: two shards)
-int32_t joint_home(const edynhip_world *w, uint32_t a, uint32_t b) {
-    const int32_t ra = w->scene.kind[a] == EDYNHIP_KIND_DYNAMIC ? w->rank_of[a] : -1, rb = w->scene.kind[b] == EDYNHIP_KIND_DYNAMIC ? w->rank_of[b] : -1;
-    if (ra >= 0 && rb >= 0) return ra == rb ? ra : -2;
-    return ra >= 0 ? ra : rb;
+// the shard a joint between global bodies a and b lives on by the partition as it stands (joint_home: -1 no context holds it, -2 two shards)
+int32_t joint_home_of(const edynhip_world *w, uint32_t a, uint32_t b) {
+    return joint_home(owner_rank(w->scene.kind[a], w->rank_of[a]), owner_rank(w->scene.kind[b], w->rank_of[b]));
 }
 
 // Rebuilds the shards marked in `force` (each with the head-room its want_bodies / want_joints ask for) through what a sticky
@@ -1695,6 +1469,24 @@ int32_t joint_home(const edynhip_world *w, uint32_t a, uint32_t b) {
 int grow_shards(edynhip_world *w, const std::vector<uint8_t> &force) {
     for (uint8_t f : force) if (f) ++w->edit_stats.shard_rebuilds;
     return repartition(w, true, nullptr, &force, true);
+}
+
+// A shard whose context cannot take its share of an edit - extra[r] more bodies, or joints - is rebuilt with head-room first, through
+// the carry. recount (or nullptr): refreshes `extra` after the rebuild (a rebalance may have moved islands). who: the entry point.
+int make_room(edynhip_world *w, bool joints, std::vector<uint32_t> &extra, const char *who, bool &grown, const std::function<int()> &recount = nullptr) {
+    const uint32_t W = (uint32_t)w->shards.size();
+    auto lacks = [&](uint32_t r) {
+        const Shard &s = w->shards[r];
+        return extra[r] && (!s.ctx || (joints ? s.local_joints.size() + extra[r] > s.joint_cap : s.local_ids.size() + extra[r] > s.cap));
+    };
+    std::vector<uint8_t> force(W, 0);
+    grown = false;
+    for (uint32_t r = 0; r < W; ++r) if (lacks(r)) { force[r] = 1; (joints ? w->shards[r].want_joints : w->shards[r].want_bodies) = extra[r]; grown = true; }
+    if (!grown) return EDYNHIP_OK;
+    EH_TRY(grow_shards(w, force));
+    if (recount) EH_TRY(recount());
+    for (uint32_t r = 0; r < W; ++r) if (lacks(r)) return w->fail(EDYNHIP_ERR_INTERNAL, std::string(who) + ": shard " + std::to_string(r) + " was rebuilt and still lacks room");
+    return EDYNHIP_OK;
 }
 
 // The safety condition after an edit that can bring islands of different shards together (a shaped dynamic body was added): the approach
@@ -1712,27 +1504,6 @@ int edit_approach(edynhip_world *w, bool &moved) {
     moved = true;
     ++w->edit_stats.repartitions_by_edit;
     return repartition(w, true, nullptr, nullptr, true);
-}
-
-// the world's query tables of shard r after bodies [l0, nl) were appended to its context
-void shard_tables_appended(edynhip_world *w, uint32_t r, uint32_t l0) {
-    Shard &s = w->shards[r];
-    const uint32_t nl = (uint32_t)s.local_ids.size();
-    if (nl == l0) return;
-    SH_HIP(s, hipMemcpy(s.ids_dev + l0, s.local_ids.data() + l0, (size_t)(nl - l0) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    std::vector<uint32_t> bits;
-    if (r != 0) {
-        bits.assign((size_t)nl / 32 + 1, 0u);
-        for (uint32_t l : s.owned_local) bits[l >> 5] |= 1u << (l & 31u);
-        SH_HIP(s, hipMemcpy(s.ans_dev, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    const uint32_t *qisl = s.ctx->query_island;
-    if (qisl) {   // the labels the shard was built with still answer the island query: a new body is an island of its own
-        std::vector<uint32_t> own(nl - l0);
-        std::iota(own.begin(), own.end(), l0);
-        SH_HIP(s, hipMemcpy(s.qisl_dev + l0, own.data(), own.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    shard_set_answers(s.ctx, r != 0 ? s.ans_dev : nullptr, std::move(bits), qisl);
 }
 
 }  // namespace
@@ -1757,85 +1528,44 @@ int edynhip_world_add_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies 
     const uint32_t n0 = sc.n, W = (uint32_t)w->shards.size();
     if (!w->built) { scene_append_bodies(w, n, in); return EDYNHIP_OK; }
     ++w->edit_stats.edits;
-    // placement: replicated, or the shard with the fewest live dynamic bodies (ties: the lowest shard), one new body after the other in
-    // index order - and with a body every later body of the call that it touches, directly or through others (the boxes of their
-    // bounding spheres within the creation margin): a pile spawned in one call lands on one shard instead of being welded together there
+    // placement (place_new_bodies): replicated, or the shard with the fewest live dynamic bodies; bodies of the call that touch (the
+    // boxes of their bounding spheres within the creation margin: estimate_islands over the new bodies alone) land on one shard
     std::vector<uint32_t> load(W, 0), extra(W, 0);
     for (uint32_t g = 0; g < n0; ++g) if (sc.kind[g] == EDYNHIP_KIND_DYNAMIC && !w->is_removed(g) && w->rank_of[g] >= 0) ++load[(uint32_t)w->rank_of[g]];
-    std::vector<int32_t> place(n, -1);
-    bool shaped_dynamic = false;
     std::vector<uint32_t> group(n);
-    std::iota(group.begin(), group.end(), 0u);
-    {
-        std::vector<IslandBox> boxes;
-        for (uint32_t k = 0; k < n; ++k) {
-            if (in->kind[k] != EDYNHIP_KIND_DYNAMIC) continue;
-            const float r = bounding_radius(sc, in->shape_type[k], in->shape_param + 4 * (size_t)k, in->center_of_mass ? in->center_of_mass + 3 * (size_t)k : nullptr);
-            if (r < 0) continue;
-            IslandBox b;
-            for (int d = 0; d < 3; ++d) { b.lo[d] = in->pos[3 * (size_t)k + d] - r; b.hi[d] = in->pos[3 * (size_t)k + d] + r; }
-            b.label = k; b.owner = 0;
-            boxes.push_back(b);
-        }
-        auto find = [&](uint32_t x) { while (group[x] != x) { group[x] = group[group[x]]; x = group[x]; } return x; };
-        sweep_boxes(boxes, kCreationMargin, false, [&](const IslandBox &a, const IslandBox &b, float) {
-            const uint32_t ra = find(a.label), rb = find(b.label);
-            if (ra != rb) group[std::max(ra, rb)] = std::min(ra, rb);
-        });
-        for (uint32_t k = 0; k < n; ++k) group[k] = find(k);   // (the root is the group's lowest index: placed before its members)
-    }
-    for (uint32_t k = 0; k < n; ++k) {
-        if (in->kind[k] != EDYNHIP_KIND_DYNAMIC) { for (uint32_t r = 0; r < W; ++r) ++extra[r]; continue; }
-        uint32_t r = 0;
-        if (group[k] != k) r = (uint32_t)place[group[k]];
-        else for (uint32_t q = 1; q < W; ++q) if (load[q] < load[r]) r = q;
-        place[k] = (int32_t)r; ++load[r]; ++extra[r];
-        if (in->shape_type[k] != EDYNHIP_SHAPE_NONE) shaped_dynamic = true;
-    }
-    // a shard whose context cannot take its share is rebuilt with head-room first, through the carry
+    MeshRadii meshes = scene_meshes(sc);
+    estimate_islands({n, in->kind, in->shape_type, in->shape_param, in->pos, in->center_of_mass}, meshes, 0, nullptr, nullptr, group.data(), nullptr);
+    const std::vector<int32_t> place = place_new_bodies(n, in->kind, group.data(), load, extra);
+    bool shaped_dynamic = false;
+    for (uint32_t k = 0; k < n; ++k) if (in->kind[k] == EDYNHIP_KIND_DYNAMIC && in->shape_type[k] != EDYNHIP_SHAPE_NONE) shaped_dynamic = true;
     bool grown = false;
-    {
-        std::vector<uint8_t> force(W, 0);
-        for (uint32_t r = 0; r < W; ++r) {
-            Shard &s = w->shards[r];
-            if (extra[r] && (!s.ctx || s.local_ids.size() + extra[r] > s.cap)) { force[r] = 1; s.want_bodies = extra[r]; grown = true; }
-        }
-        if (grown) {
-            EH_TRY(grow_shards(w, force));
-            for (uint32_t r = 0; r < W; ++r)
-                if (extra[r] && (!w->shards[r].ctx || w->shards[r].local_ids.size() + extra[r] > w->shards[r].cap))
-                    return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_bodies: shard " + std::to_string(r) + " was rebuilt and still lacks room");
-        }
-    }
+    EH_TRY(make_room(w, false, extra, "edynhip_world_add_bodies", grown));
     scene_append_bodies(w, n, in);
     for (uint32_t k = 0; k < n; ++k) w->rank_of.push_back(place[k]);
     w->pos.insert(w->pos.end(), in->pos, in->pos + 3 * (size_t)n); w->orn.insert(w->orn.end(), in->orn, in->orn + 4 * (size_t)n);
     w->linvel.insert(w->linvel.end(), in->linvel, in->linvel + 3 * (size_t)n); w->angvel.insert(w->angvel.end(), in->angvel, in->angvel + 3 * (size_t)n);
     if (w->query_labels.size() == n0) for (uint32_t k = 0; k < n; ++k) w->query_labels.push_back(n0 + k);
-    w->pool->run([&](uint32_t r) {
-        Shard &s = w->shards[r];
-        s.rc = EDYNHIP_OK; s.err.clear();
-        s.to_local.resize((size_t)n0 + n, -1);
-        std::vector<uint32_t> mine;
-        for (uint32_t k = 0; k < n; ++k) if (place[k] == (int32_t)r || place[k] < 0) mine.push_back(k);
-        if (mine.empty()) return;
-        SH_HIP(s, hipSetDevice(s.device));
-        const BodyRows sub(*in, mine);
+    std::vector<std::vector<uint32_t>> mine(W);
+    for (uint32_t r = 0; r < W; ++r) {
+        w->shards[r].to_local.resize((size_t)n0 + n, -1);
+        for (uint32_t k = 0; k < n; ++k) if (shard_holds_body(place[k], r)) mine[r].push_back(k);
+    }
+    EH_TRY(on_shards(w, [&](Shard &, uint32_t r) { return !mine[r].empty(); }, [&](Shard &s, uint32_t r) {
+        const BodyRows sub(*in, mine[r]);
         const edynhip_bodies b = sub.view();
-        SH_TRY(s, edynhip_add_bodies(s.ctx, (uint32_t)mine.size(), &b));
+        SH_TRY(s, edynhip_add_bodies(s.ctx, (uint32_t)mine[r].size(), &b));
         const uint32_t l0 = (uint32_t)s.local_ids.size();
-        for (uint32_t k : mine) {
+        for (uint32_t k : mine[r]) {
             const uint32_t l = (uint32_t)s.local_ids.size();
             s.to_local[n0 + k] = (int32_t)l;
-            if (place[k] == (int32_t)r || r == 0) s.owned_local.push_back(l);
+            if (shard_reports_body(place[k], r)) s.owned_local.push_back(l);
             s.local_ids.push_back(n0 + k);
         }
-        shard_tables_appended(w, r, l0);
+        upload_query_tables(w, r, l0);
         if (s.rc != EDYNHIP_OK) return;
         gather_shard(w, r, false);   // the state the context holds for them (the centre of mass where the caller gave an origin)
-    });
-    EH_TRY(shard_error(w));
-    for (uint32_t r = 0; r < W; ++r) w->stats.bodies_per_shard[r < 16 ? r : 15] = (uint32_t)w->shards[r].owned_local.size();
+    }));
+    refresh_bodies_per_shard(w);
     bool moved = false;
     if (shaped_dynamic) EH_TRY(edit_approach(w, moved));
     if (!grown && !moved) ++w->edit_stats.in_place;
@@ -1852,16 +1582,14 @@ int edynhip_world_remove_bodies(edynhip_world *w, uint32_t n, const uint32_t *in
     w->removed.resize(sc.n, 0);
     if (w->built) {
         ++w->edit_stats.edits;
-        w->pool->run([&](uint32_t r) {   // the owner of a dynamic body, every shard for a replicated one
-            Shard &s = w->shards[r];
-            s.rc = EDYNHIP_OK; s.err.clear();
-            std::vector<uint32_t> mine;
-            for (uint32_t g : gone) if (g < s.to_local.size() && s.to_local[g] >= 0) mine.push_back((uint32_t)s.to_local[g]);
-            if (mine.empty() || !s.ctx) return;
-            SH_HIP(s, hipSetDevice(s.device));
-            SH_TRY(s, edynhip_remove_bodies(s.ctx, (uint32_t)mine.size(), mine.data()));
-        });
-        EH_TRY(shard_error(w));
+        std::vector<std::vector<uint32_t>> mine(w->shards.size());   // the owner of a dynamic body, every shard for a replicated one
+        for (uint32_t r = 0; r < w->shards.size(); ++r) {
+            const Shard &s = w->shards[r];
+            for (uint32_t g : gone) if (g < s.to_local.size() && s.to_local[g] >= 0) mine[r].push_back((uint32_t)s.to_local[g]);
+        }
+        EH_TRY(on_shards(w, [&](Shard &s, uint32_t r) { return !mine[r].empty() && s.ctx; }, [&](Shard &s, uint32_t r) {
+            SH_TRY(s, edynhip_remove_bodies(s.ctx, (uint32_t)mine[r].size(), mine[r].data()));
+        }));
         ++w->edit_stats.in_place;
     }
     scene_tombstones(w, gone);
@@ -1883,68 +1611,49 @@ int edynhip_world_add_joints(edynhip_world *w, uint32_t n, const edynhip_joints 
         if (in->type[e] == EDYNHIP_JOINT_HINGE && !in->axis) return w->fail(EDYNHIP_ERR_INVALID, "edynhip_world_add_joints: hinge needs axes");
     }
     const uint32_t nj0 = sc.nj, W = (uint32_t)w->shards.size();
-    auto append_scene = [&] {
-        sc.jtype.insert(sc.jtype.end(), in->type, in->type + n); sc.jbody.insert(sc.jbody.end(), in->body, in->body + 2 * (size_t)n);
-        sc.jpivot.insert(sc.jpivot.end(), in->pivot, in->pivot + 6 * (size_t)n);
-        if (in->axis) sc.jaxis.insert(sc.jaxis.end(), in->axis, in->axis + 6 * (size_t)n); else sc.jaxis.resize(sc.jaxis.size() + 6 * (size_t)n, 0.f);
-        if (in->params) sc.jparams.insert(sc.jparams.end(), in->params, in->params + 10 * (size_t)n); else sc.jparams.resize(sc.jparams.size() + 10 * (size_t)n, 0.f);
-        sc.jalive.resize((size_t)nj0 + n, 1);
-        sc.nj = nj0 + n;
-    };
-    if (!w->built) { append_scene(); return EDYNHIP_OK; }
+    if (!w->built) { scene_append_joints(sc, n, in); return EDYNHIP_OK; }
     ++w->edit_stats.edits;
     // a joint between two shards: its islands move together first (the welding unites the pair), then the joint is made in place
     bool moved = false;
     {
         std::vector<std::array<uint32_t, 2>> edges;
-        for (uint32_t e = 0; e < n; ++e) if (joint_home(w, in->body[2 * e], in->body[2 * e + 1]) == -2) edges.push_back({in->body[2 * e], in->body[2 * e + 1]});
+        for (uint32_t e = 0; e < n; ++e) if (joint_home_of(w, in->body[2 * e], in->body[2 * e + 1]) == -2) edges.push_back({in->body[2 * e], in->body[2 * e + 1]});
         if (!edges.empty()) {
             moved = true;
             ++w->edit_stats.repartitions_by_edit;
             EH_TRY(repartition(w, true, &edges, nullptr, true));
-            for (const auto &e : edges) if (joint_home(w, e[0], e[1]) == -2) return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: the re-partition left a joint's bodies on two shards");
+            for (const auto &e : edges) if (joint_home_of(w, e[0], e[1]) == -2) return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: the re-partition left a joint's bodies on two shards");
         }
     }
     std::vector<int32_t> home(n);
     std::vector<uint32_t> extra(W, 0);
-    for (uint32_t e = 0; e < n; ++e) { home[e] = joint_home(w, in->body[2 * e], in->body[2 * e + 1]); if (home[e] >= 0) ++extra[(uint32_t)home[e]]; }
+    auto count_homes = [&]() -> int {   // (again after shards were rebuilt: a rebalance may have moved islands)
+        std::fill(extra.begin(), extra.end(), 0u);
+        for (uint32_t e = 0; e < n; ++e) {
+            home[e] = joint_home_of(w, in->body[2 * e], in->body[2 * e + 1]);
+            if (home[e] == -2) return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: a joint's bodies are on two shards");
+            if (home[e] >= 0) ++extra[(uint32_t)home[e]];
+        }
+        return EDYNHIP_OK;
+    };
+    EH_TRY(count_homes());
     bool grown = false;
-    {
-        std::vector<uint8_t> force(W, 0);
-        for (uint32_t r = 0; r < W; ++r) {
-            Shard &s = w->shards[r];
-            if (extra[r] && (!s.ctx || s.local_joints.size() + extra[r] > s.joint_cap)) { force[r] = 1; s.want_joints = extra[r]; grown = true; }
-        }
-        if (grown) {
-            EH_TRY(grow_shards(w, force));
-            for (uint32_t e = 0; e < n; ++e) home[e] = joint_home(w, in->body[2 * e], in->body[2 * e + 1]);   // (a rebalance may have moved islands)
-            std::fill(extra.begin(), extra.end(), 0u);
-            for (uint32_t e = 0; e < n; ++e) { if (home[e] == -2) return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: a joint's bodies are on two shards"); if (home[e] >= 0) ++extra[(uint32_t)home[e]]; }
-            for (uint32_t r = 0; r < W; ++r)
-                if (extra[r] && w->shards[r].local_joints.size() + extra[r] > w->shards[r].joint_cap)
-                    return w->fail(EDYNHIP_ERR_INTERNAL, "edynhip_world_add_joints: shard " + std::to_string(r) + " was rebuilt and still lacks room");
-        }
-    }
-    w->pool->run([&](uint32_t r) {
-        Shard &s = w->shards[r];
-        s.rc = EDYNHIP_OK; s.err.clear();
-        std::vector<uint32_t> mine;
-        for (uint32_t e = 0; e < n; ++e) if (home[e] == (int32_t)r) mine.push_back(e);
-        if (mine.empty()) return;
-        SH_HIP(s, hipSetDevice(s.device));
-        auto jt = rows_of(in->type, mine, 1);
-        auto jb = rows_of(in->body, mine, 2);
+    EH_TRY(make_room(w, true, extra, "edynhip_world_add_joints", grown, count_homes));
+    std::vector<std::vector<uint32_t>> mine(W);
+    for (uint32_t e = 0; e < n; ++e) if (home[e] >= 0) mine[(uint32_t)home[e]].push_back(e);
+    EH_TRY(on_shards(w, [&](Shard &, uint32_t r) { return !mine[r].empty(); }, [&](Shard &s, uint32_t r) {
+        auto jt = rows_of(in->type, mine[r], 1);
+        auto jb = rows_of(in->body, mine[r], 2);
         for (uint32_t &x : jb) x = (uint32_t)s.to_local[x];
-        auto jp = rows_of(in->pivot, mine, 6), ja = rows_of(in->axis, mine, 6), jq = rows_of(in->params, mine, 10);
+        auto jp = rows_of(in->pivot, mine[r], 6), ja = rows_of(in->axis, mine[r], 6), jq = rows_of(in->params, mine[r], 10);
         edynhip_joints j{};
         j.type = jt.data(); j.body = jb.data(); j.pivot = jp.data(); j.axis = ja.empty() ? nullptr : ja.data(); j.params = jq.empty() ? nullptr : jq.data();
         uint32_t first = 0;
-        SH_TRY(s, edynhip_add_joints(s.ctx, (uint32_t)mine.size(), &j, &first));
+        SH_TRY(s, edynhip_add_joints(s.ctx, (uint32_t)mine[r].size(), &j, &first));
         if (first != s.local_joints.size()) { s.rc = EDYNHIP_ERR_INTERNAL; s.err = "the context's joint indices and the shard's joint map disagree"; return; }
-        for (uint32_t e : mine) s.local_joints.push_back(nj0 + e);
-    });
-    EH_TRY(shard_error(w));
-    append_scene();
+        for (uint32_t e : mine[r]) s.local_joints.push_back(nj0 + e);
+    }));
+    scene_append_joints(sc, n, in);
     if (!grown && !moved) ++w->edit_stats.in_place;
     return EDYNHIP_OK;
 }
@@ -1960,14 +1669,9 @@ int edynhip_world_remove_joints(edynhip_world *w, uint32_t n, const uint32_t *in
         ++w->edit_stats.edits;
         std::vector<std::vector<uint32_t>> mine(w->shards.size());
         for (uint32_t j : gone) { uint32_t l = 0; const int32_t r = joint_shard(w, j, l); if (r >= 0) mine[(uint32_t)r].push_back(l); }
-        w->pool->run([&](uint32_t r) {
-            Shard &s = w->shards[r];
-            s.rc = EDYNHIP_OK; s.err.clear();
-            if (mine[r].empty()) return;
-            SH_HIP(s, hipSetDevice(s.device));
+        EH_TRY(on_shards(w, [&](Shard &, uint32_t r) { return !mine[r].empty(); }, [&](Shard &s, uint32_t r) {
             SH_TRY(s, edynhip_remove_joints(s.ctx, (uint32_t)mine[r].size(), mine[r].data()));
-        });
-        EH_TRY(shard_error(w));
+        }));
         ++w->edit_stats.in_place;
     }
     for (uint32_t j : gone) sc.jalive[j] = 0;
@@ -1998,9 +1702,7 @@ int edynhip_world_edit_joint(edynhip_world *w, uint32_t joint, const float *fram
         ++w->edit_stats.in_place;
     }
     if (generic < 0) { std::memcpy(&sc.jparams[10 * (size_t)joint], params, 10 * sizeof(float)); return EDYNHIP_OK; }
-    HostScene::Def d;
-    d.joint = joint; d.generic = generic != 0;
-    d.fa.assign(frame_a9, frame_a9 + 9); d.fb.assign(frame_b9, frame_b9 + 9); d.p.assign(params, params + (generic ? 60 : 16));
+    HostScene::Def d = make_def(joint, frame_a9, frame_b9, params, generic != 0);
     for (HostScene::Def &old : sc.defs) if (old.joint == joint && old.generic == d.generic) { old = std::move(d); return EDYNHIP_OK; }
     sc.defs.push_back(std::move(d));
     return EDYNHIP_OK;
@@ -2023,7 +1725,7 @@ int edynhip_world_edit_exclusion(edynhip_world *w, uint32_t a, uint32_t b, int e
         ++w->edit_stats.edits;
         for (uint32_t r = 0; r < w->shards.size(); ++r) {   // the shard build_shard gives the pair to; a pair on two shards is the scene's until its bodies meet
             Shard &s = w->shards[r];
-            if (!s.ctx || s.to_local[a] < 0 || s.to_local[b] < 0 || !(w->rank_of[a] == (int32_t)r || w->rank_of[b] == (int32_t)r)) continue;
+            if (!s.ctx || !shard_holds_exclusion(w->rank_of[a], w->rank_of[b], r)) continue;
             W_HIP(w, hipSetDevice(s.device));
             const int rc = exclude ? edynhip_exclude_collision(s.ctx, (uint32_t)s.to_local[a], (uint32_t)s.to_local[b]) : edynhip_remove_collision_exclusion(s.ctx, (uint32_t)s.to_local[a], (uint32_t)s.to_local[b]);
             if (rc != EDYNHIP_OK) return w->fail(rc, std::string("edynhip_world_edit_exclusion: shard ") + std::to_string(r) + ": " + edynhip_last_error(s.ctx));
@@ -2048,15 +1750,10 @@ int edynhip_world_set_state(edynhip_world *w, const float *pos, const float *orn
     EH_TRY(ensure_built(w));
     ++w->edit_stats.edits;
     w->pos.assign(pos, pos + 3 * n); w->orn.assign(orn, orn + 4 * n); w->linvel.assign(linvel, linvel + 3 * n); w->angvel.assign(angvel, angvel + 3 * n);
-    w->pool->run([&](uint32_t r) {
-        Shard &s = w->shards[r];
-        s.rc = EDYNHIP_OK; s.err.clear();
-        if (s.local_ids.empty() || !s.ctx) return;
-        SH_HIP(s, hipSetDevice(s.device));
+    EH_TRY(on_shards(w, [](Shard &s, uint32_t) { return !s.local_ids.empty() && s.ctx; }, [&](Shard &s, uint32_t) {
         auto p = take(w->pos, s.local_ids, 3), q = take(w->orn, s.local_ids, 4), v = take(w->linvel, s.local_ids, 3), o = take(w->angvel, s.local_ids, 3);
         SH_TRY(s, edynhip_set_state(s.ctx, p.data(), q.data(), v.data(), o.data()));
-    });
-    EH_TRY(shard_error(w));
+    }));
     // A context's boxes follow the new state at the end of its next step (edynhip_set_state), which is when its broadphase - and the growth
     // monitor - first see where the bodies went: the approach check is due right after that step, whatever the budget said before.
     w->budget = 0.0f;
@@ -2103,16 +1800,11 @@ int edynhip_world_get_asleep(edynhip_world *w, uint8_t *asleep) {
     EH_TRY(ensure_built(w));
     std::memset(asleep, 0, w->scene.n);
     if (!(w->cfg.flags & EDYNHIP_FLAG_SLEEPING)) return EDYNHIP_OK;
-    w->pool->run([&](uint32_t r) {   // every body's tag from the shard that reports its state
-        Shard &s = w->shards[r];
-        s.rc = EDYNHIP_OK; s.err.clear();
-        if (s.local_ids.empty() || !s.ctx) return;
-        SH_HIP(s, hipSetDevice(s.device));
+    return on_shards(w, [](Shard &s, uint32_t) { return !s.local_ids.empty() && s.ctx; }, [&](Shard &s, uint32_t) {   // every body's tag from the shard that reports its state
         s.asleep.assign(s.local_ids.size(), 0);
         SH_TRY(s, edynhip_get_asleep(s.ctx, s.asleep.data()));
         for (uint32_t l : s.owned_local) asleep[s.local_ids[l]] = s.asleep[l];
     });
-    return shard_error(w);
 }
 
 int edynhip_world_get_edit_stats(edynhip_world *w, edynhip_world_edit_stats *out) {
