@@ -4,6 +4,7 @@
 // solver's by-index gathers fetch a whole component in one transaction.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -12,6 +13,7 @@
 #include <vector>
 #include "../../include/edynhip.h"
 #include "dmesh.hpp"
+#include "hipown.hpp"
 
 namespace eh {
 
@@ -316,6 +318,10 @@ struct StageTimer {
     uint32_t capacity = 0;          // steps for which events exist
     hipEvent_t *e = nullptr;        // events of the step being recorded (nullptr = not recording)
     uint32_t mask = 0;              // which of the kEvents are recorded (an event record idles the GPU ~6 us)
+    StageTimer() = default;
+    StageTimer(const StageTimer &) = delete;
+    StageTimer &operator=(const StageTimer &) = delete;
+    ~StageTimer() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); }   // the timer owns its events (solver.hip records them through `e`)
 };
 
 #define B_POS(b, i) ((b).xf[8 * (size_t)(i)])
@@ -326,6 +332,50 @@ struct StageTimer {
 #define B_ORG(b, i) (((b).origin && (b).com[(i)].w != 0.0f) ? from4((b).origin[(i)]) : from4(B_POS(b, i)))
 #define B_DV(b, i) ((b).dvw[2 * (size_t)(i)])
 #define B_DW(b, i) ((b).dvw[2 * (size_t)(i) + 1])
+
+// ---- what only the C-ABI files touch, grouped by concern. Pinned memory, events and the side stream are held by owners (hipown.hpp)
+// and go with the context; device memory made by dalloc() belongs to the context's arena (edynhip_ctx::allocs).
+// capi_scene.hip: index lists handed to small kernels (bodies to wake, bodies to remove) - one device buffer that grows on demand
+struct IndexScratch { DeviceBuf<uint32_t> buf; size_t cap = 0; };
+// capi_readback.hip get / set_state: [max_bodies][13] staging of the packed state (both run every update in the C++ shim)
+struct StateStaging { float *dev = nullptr; PinnedBuf<float> host; };
+// capi_scene.hip: host mirror of edynhip_ctx::excl (edits are rare: scene construction) and the body rows of it edited since the last
+// upload (flush_exclusions)
+struct ExclusionLists { std::vector<uint32_t> host; uint32_t dirty_lo = 0xFFFFFFFFu, dirty_hi = 0; };
+// capi_scene.hip: the material mix table, host side: the reference's container (std::map under unordered_pair's comparator) so that
+// lookups behave exactly like its own; ids by body; the device buffers are rebuilt on every change (rebuild_mix_table)
+struct MixIdPair { uint32_t first, second; };
+struct MixIdPairLess {
+    bool operator()(const MixIdPair &a, const MixIdPair &b) const {   // core/unordered_pair.hpp:32-40
+        if (a.first == b.second && a.second == b.first) return false;
+        if (a.first == b.first) return a.second < b.second;
+        return a.first < b.first;
+    }
+};
+struct MixTable {
+    std::map<MixIdPair, std::array<float, 6>, MixIdPairLess> host;
+    std::vector<uint32_t> mat_id;   // per body, 0xFFFF = material::UnassignedID
+    uint32_t *d_mat_cid = nullptr; int32_t *d_lut = nullptr; float *d_vals = nullptr; uint32_t lut_cap = 0, vals_cap = 0;
+};
+// capi_readback.hip: the stream the read-back copies run on, beside the stepper's, and the event that orders it behind the stepper
+struct SideStream { Stream stream; Event ready; };
+// double-buffered read-back (edynhip_snapshot): pinned host copies of the packed state, the event that completes each
+struct SnapshotSlots {
+    PinnedBuf<float> host[2]; float *dev[2] = {nullptr, nullptr}; Event event[2];
+    uint32_t step[2] = {0, 0}, bodies[2] = {0, 0}; int last = -1;
+};
+// record snapshots (edynhip_snapshot_records, ABI 15): per slot one device block and its pinned host copy, laid out as
+// [header 64 B | events: event_cap x 24 B | records: bodies x 96 B]; the registry write-back reads the pinned copy in place
+struct RecordSlots {
+    PinnedBuf<uint8_t> host[2]; uint8_t *dev[2] = {nullptr, nullptr}; Event event[2];
+    uint32_t step[2] = {0, 0}, bodies[2] = {0, 0}, events_copied[2] = {0, 0}; int last = -1; uint32_t event_cap = 0;
+};
+// contact-event prefetch (edynhip_set_event_prefetch): the event list of a step call copied to pinned memory as soon as the last step's
+// narrowphase has run - the caller turns it into registry entities while the solve is still running
+struct EventPrefetch {
+    uint32_t max = 0; PinnedBuf<uint8_t> host; Event np_done, ready; bool now = false;
+    int state = 0;   // 0 none, 1 copy enqueued, 2 the call ran no step
+};
 
 }  // namespace eh
 
@@ -343,7 +393,7 @@ struct edynhip_ctx {
     uint32_t num_manifolds = 0;    // in m[cur]
     eh::Joints j;
     std::vector<eh::HostJoint> host_joints;   // by caller index (see HostJoint)
-    std::vector<uint32_t> pending_redefs;     // joints edited since the device arrays were built (capi.hip flush_joint_redefs)
+    std::vector<uint32_t> pending_redefs;     // joints edited since the device arrays were built (capi_scene.hip flush_joint_redefs)
     eh::Rows rows;
     eh::LBVH bvh;
     float4 *np_ra = nullptr, *np_rb = nullptr, *np_rn = nullptr;   // narrowphase staging: the raw collide() result per manifold
@@ -388,12 +438,12 @@ struct edynhip_ctx {
     uint32_t colour_start[eh::kMaxColours] = {0}, colour_end[eh::kMaxColours] = {0};
     uint32_t colour_split[eh::kMaxColours][3] = {{0}};   // ends of the 4-, 3- and 2-point groups inside each colour's range
     uint32_t num_active = 0;
-    std::vector<void *> allocs;
-    uint32_t *idx_scratch = nullptr; size_t idx_scratch_cap = 0;   // index lists of the editing entry points (capi.hip index_scratch)
+    std::vector<void *> allocs;    // the device arena: everything dalloc() made, released by edynhip_destroy
+    eh::PinnedBuf<eh::Counters> cnt_host_mem; eh::PinnedBuf<uint32_t> cnt_seq_mem;   // owners of cnt_host / cnt_seq
+    eh::IndexScratch idx_scratch;
     bool clears_primed = false;    // the previous call ended with k_finish, which pre-clears the next step's scratch
     bool full_step = false;        // inside edynhip_step (all stages back to back): per-step clears are folded into kernels
-    float *state_dev = nullptr;    // [max_bodies][13] staging of the packed state (get/set_state run every update in the C++ shim)
-    float *state_host = nullptr;   // pinned mirror
+    eh::StateStaging state;
     bool sleeping = false;         // EDYNHIP_FLAG_SLEEPING
     bool all_asleep = false;       // the last step left every procedural body asleep and nothing was edited since: steps are no-ops
     bool solve_begin_done = false; // this step's k_cc_flatten already did k_solve_begin's work (islands.hip islands())
@@ -413,26 +463,13 @@ struct edynhip_ctx {
     uint32_t *rot_off = nullptr;             // per body: its slice of `rot` (~0u: none)
     std::vector<uint32_t> host_rot_off;
     uint32_t *poly_work = nullptr;           // narrowphase.hip PolyBins: bin counters + per-manifold keys + the binned manifold list
-    // material mix table, host side: the reference's container (std::map under unordered_pair's comparator) so that lookups behave
-    // exactly like its own; ids by body; device buffers are rebuilt on every change (rebuild_mix_table, capi.hip)
-    struct MixIdPair { uint32_t first, second; };
-    struct MixIdPairLess {
-        bool operator()(const MixIdPair &a, const MixIdPair &b) const {   // core/unordered_pair.hpp:32-40
-            if (a.first == b.second && a.second == b.first) return false;
-            if (a.first == b.first) return a.second < b.second;
-            return a.first < b.first;
-        }
-    };
-    std::map<MixIdPair, std::array<float, 6>, MixIdPairLess> host_mix;
-    std::vector<uint32_t> host_mat_id;   // per body, 0xFFFF = material::UnassignedID
-    uint32_t *d_mat_cid = nullptr; int32_t *d_mix_lut = nullptr; float *d_mix_vals = nullptr; uint32_t mix_lut_cap = 0, mix_vals_cap = 0;
+    eh::MixTable mix;
     bool extras = false;           // some body carries a contact_extras material: extras storage exists, per-colour schedule
     uint32_t step_index = 0;       // completed steps
     // contact events: device list of the current edynhip_step call, per-manifold "still there" marks of the previous array
     eh::ContactEvent *events = nullptr; uint32_t *event_count = nullptr; uint32_t event_cap = 0; uint8_t *prev_matched = nullptr;
-    // double-buffered read-back (edynhip_snapshot): pinned host copies of the packed state, the event that completes each
-    float *snap_host[2] = {nullptr, nullptr}; float *snap_dev[2] = {nullptr, nullptr}; hipEvent_t snap_event[2] = {nullptr, nullptr};
-    uint32_t snap_step[2] = {0, 0}, snap_bodies[2] = {0, 0}; int snap_last = -1; hipStream_t snap_stream = nullptr; hipEvent_t snap_ready = nullptr;
+    eh::SideStream side;           // read-back beside the stepper's stream (capi_readback.hip)
+    eh::SnapshotSlots snap;
     // Bodies that CAN sleep (dynamic, not sleeping_disabled) ever uploaded (removals are not subtracted: an upper bound). While it is zero
     // the island-sleeping stage has nothing to decide - every island carries SL_DISABLED (the reference's exclude_sleeping_disabled views
     // skip such entities, island_manager.cpp:573-623) - and its kernels are not launched: a benchmark scene, sleeping_disabled on every
@@ -441,14 +478,8 @@ struct edynhip_ctx {
     bool sleep_active() const { return sleeping && num_sleepable > 0; }
     unsigned long long *pp_prof_dev = nullptr; int pp_prof_calls = 0;   // EDYNHIP_PP_PROF (narrowphase.hip): phase ticks of the polyhedron-pair kernels
     bool island_labels_valid = false;   // b.island / sleep_since hold what an island stage (or edynhip_set_sleep_timers) wrote - not before the first step of a new scene
-    uint32_t excl_dirty_lo = 0xFFFFFFFFu, excl_dirty_hi = 0;   // body rows of host_excl edited since the last upload (capi.hip flush_exclusions)
-    // contact-event prefetch (edynhip_set_event_prefetch): the event list of a step call copied to pinned memory as soon as the last step's
-    // narrowphase has run - the caller turns it into registry entities while the solve is still running
-    uint32_t evp_max = 0; uint8_t *evp_host = nullptr; hipEvent_t evp_np_done = nullptr, evp_ready = nullptr; bool evp_now = false; int evp_state = 0;   // 0 none, 1 copy enqueued, 2 the call ran no step
-    // record snapshots (edynhip_snapshot_records, ABI 15): per slot one device block and its pinned host copy, laid out as
-    // [header 64 B | events: rec_event_cap x 24 B | records: bodies x 96 B]; the registry write-back reads the pinned copy in place
-    uint8_t *rec_host[2] = {nullptr, nullptr}; uint8_t *rec_dev[2] = {nullptr, nullptr}; hipEvent_t rec_event[2] = {nullptr, nullptr};
-    uint32_t rec_step[2] = {0, 0}, rec_bodies[2] = {0, 0}, rec_events_copied[2] = {0, 0}; int rec_last = -1; uint32_t rec_event_cap = 0;
+    eh::EventPrefetch evp;
+    eh::RecordSlots rec;
     // Island sleep timers run on the step time stamps the stepper hands to the island manager (stepper_sequential.cpp:60-75,
     // island_manager.cpp:533-539,605-623): sim_clock is the island manager's m_last_time, i.e. the stamp of the PREVIOUS step while
     // a step runs - advanced by fixed_dt per edynhip_step step, set by the caller in edynhip_step_timed (the
@@ -481,8 +512,8 @@ struct edynhip_ctx {
     uint8_t *rstar = nullptr;
     uint64_t *rbest = nullptr;
     float4 *rimp = nullptr;
-    uint32_t *excl = nullptr;      // collision exclusion lists [max_bodies][16], ~0u-terminated; allocated by the first edynhip_exclude_collision
-    std::vector<uint32_t> host_excl;   // host mirror of excl (edits are rare: scene construction)
+    uint32_t *excl = nullptr;      // collision exclusion lists [max_bodies][16], ~0u-terminated (read by the broadphase); allocated by the first upload of an exclusion
+    eh::ExclusionLists exclusions; // their host mirror
     std::vector<int32_t> host_kind, host_shape;   // per body, for rebuilding the broadphase lists when bodies are appended
     // raycast queries (raycast.hip): a query tree of their own, rebuilt at the first raycast after state_epoch moved on
     uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
@@ -503,6 +534,38 @@ struct edynhip_ctx {
 };
 
 namespace eh {
+// ---- What an edit invalidates. The host keeps six facts about the device state between calls; an entry point that edits the world
+// names what it did, and these functions say which facts that costs (x). Call sites set nothing by hand.
+//   force_islands     the island labels are recomputed in full by the next step (they or the constraint graph changed behind it)
+//   all_asleep        "every procedural body sleeps, steps are no-ops" no longer holds
+//   clears_primed     the next step clears its scratch itself (what k_finish pre-cleared no longer fits)
+//   lists_dirty       the broadphase rebuilds its candidate lists at the next step
+//   state_epoch       the query trees of raycast.hip / query_aabb.hip are stale
+//   topology_epoch    the cached island lists and largest-island figures of the solve's schedule are stale
+//
+//                              force_islands  all_asleep=false  clears_primed=false  lists_dirty  ++state_epoch  ++topology_epoch
+//   bodies_moved                                                                          x            x            set_state, refresh_derived, set_center_of_mass
+//   step_began                                                                                         x            run_stages: the broadphase looks after its own lists
+//   body_set_changed                               x                                      x            x            rebuild_broadphase_lists (set / add / remove bodies)
+//   contact_state_replaced          x              x                  x                                             set / add / remove bodies, set_manifolds
+//   topology_changed                                                                                              x  load_bodies, rebuild_joints
+//   graph_changed(woke = true)      x              x                                                                rebuild_joints, set_asleep
+//   graph_changed(woke = false)     x                                                                               set_sleep_timers, a partial run_stages
+//   woke                                           x                                                                wake_all, wake_islands_of
+//   step_failed                     x                                 x (and full_step)                             a stage of run_stages failed
+// Differences between look-alikes that are kept as they are: edynhip_remove_bodies does not bump topology_epoch itself (only through the
+// joints it removes) where load_bodies does, and load_bodies bumps it before it has validated its arguments; edynhip_set_sleep_timers
+// forces the relabel without touching all_asleep where edynhip_set_asleep does both; edynhip_set_center_of_mass wakes nobody where
+// edynhip_set_state wakes everybody; rebuild_joints bumps topology_epoch before its capacity check and marks the graph after it.
+inline void invalidate_bodies_moved(edynhip_ctx *c) { c->bvh.lists_dirty = true; ++c->state_epoch; }
+inline void invalidate_step_began(edynhip_ctx *c) { ++c->state_epoch; }
+inline void invalidate_woke(edynhip_ctx *c) { c->all_asleep = false; }
+inline void invalidate_body_set_changed(edynhip_ctx *c) { c->all_asleep = false; c->bvh.lists_dirty = true; ++c->state_epoch; }
+inline void invalidate_contact_state_replaced(edynhip_ctx *c) { c->force_islands = true; c->all_asleep = false; c->clears_primed = false; }
+inline void invalidate_topology_changed(edynhip_ctx *c) { ++c->topology_epoch; }
+inline void invalidate_graph_changed(edynhip_ctx *c, bool woke) { c->force_islands = true; if (woke) c->all_asleep = false; }
+inline void invalidate_step_failed(edynhip_ctx *c) { c->clears_primed = false; c->full_step = false; c->force_islands = true; }
+
 // stage entry points (each .hip file implements its own)
 int broadphase(edynhip_ctx *c);
 int narrowphase(edynhip_ctx *c);
@@ -521,9 +584,15 @@ Knobs read_knobs();   // capi.hip: the only function that reads EDYNHIP_* variab
 inline EventSink event_sink(const edynhip_ctx *c) { return EventSink{c->events, c->event_count, c->event_cap, c->event_step_base + c->step_index, c->event_id_tag}; }
 int restitution(edynhip_ctx *c);   // restitution.hip: solve_restitution, before gravity and the constraint solver (solver.cpp:397)
 int solve(edynhip_ctx *c);
-int refresh_derived(edynhip_ctx *c);
+int refresh_derived(edynhip_ctx *c);   // AABBs + world inertias from the current transforms (solver.hip)
 int joint_reset_angles(edynhip_ctx *c, const uint8_t *which_dev);   // reset_angle of the marked (sorted-order) joints
-int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies);   // capi.hip   // AABBs + world inertias from the current transforms (solver.hip)
+int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies);   // capi_scene.hip
+// Shared by the C-ABI files only (they were one file's statics): kept out of the library's exported symbols.
+#define EH_LOCAL __attribute__((visibility("hidden")))
+// capi_scene.hip: what the step entry points (capi.hip) and the state edits (capi_readback.hip) bring up to date first
+EH_LOCAL int flush_joint_redefs(edynhip_ctx *c);   // joints redefined since the device arrays were built
+EH_LOCAL int flush_exclusions(edynhip_ctx *c);     // exclusion rows edited since the last upload
+EH_LOCAL int enqueue_event_prefetch(edynhip_ctx *c);   // capi_readback.hip: this call's event count and list -> the pinned prefetch buffer
 // sort helpers (sort.hip)
 size_t sort_temp_bytes(uint32_t max_items);
 int sort_u64(edynhip_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n, int begin_bit, int end_bit);
@@ -565,3 +634,17 @@ int shard_pack_records(edynhip_ctx *c, const uint32_t *local_ids_dev, uint32_t n
         int r__ = (expr);               \
         if (r__ != EDYNHIP_OK) return r__; \
     } while (0)
+
+namespace eh {
+// Zeroed device memory that lives as long as the context (its arena, edynhip_ctx::allocs). Used by the C-ABI files.
+template <typename T>
+static int dalloc(edynhip_ctx *c, T *&p, size_t count) {
+    void *q = nullptr;
+    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    EH_HIP(c, hipMalloc(&q, bytes));
+    EH_HIP(c, hipMemsetAsync(q, 0, bytes, c->stream));
+    c->allocs.push_back(q);
+    p = (T *)q;
+    return EDYNHIP_OK;
+}
+}  // namespace eh
