@@ -53,7 +53,10 @@ DI f3 normalize(f3 a) { return a / length(a); }   // vector3.hpp:231-235 (true d
 DI float distance_sqr(f3 a, f3 b) { return length_sqr(a - b); }
 DI f3 project_plane(f3 p, f3 q, f3 n) { return p - n * dot(p - q, n); }
 DI f3 lerp(f3 a, f3 b, float s) { return a * (1.0f - s) + b * s; }
-DI float clamp_unit(float s) { return fminf(fmaxf(s, 0.0f), 1.0f); }
+// math.hpp:46-48: std::clamp(s, 0, 1), spelt as the comparisons it is made of. fminf(fmaxf(s, 0), 1) agrees on ordinary numbers only:
+// the hardware max turns a NaN into 0 and a -0.0 into +0.0, std::clamp hands both back as they came (a NaN reaches this from
+// intersect_segments when a segment has no length in the plane, geom.cpp:826-838: 0 * (1 / 0)).
+DI float clamp_unit(float s) { return s < 0.0f ? 0.0f : (1.0f < s ? 1.0f : s); }
 DI float square(float s) { return s * s; }
 DI float comp(f3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 DI bool try_normalize(f3 &v) {

@@ -75,3 +75,84 @@ def pair_batch(rng, n, tA, tB, mesh_radii=None):
     else:
         pos[:, 1] = pos[:, 0] + d * (reach[:, 0] + reach[:, 1] + gap)[:, None]
     return st, sp, pos.astype(np.float32), orn.astype(np.float32)
+
+
+EDGE_CLASSES = ("coincident", "deep", "far", "scale", "aspect", "lattice")
+LATTICE_THRESHOLDS = (0.02, 0.25)   # at 0.25 a grid separation can equal the threshold exactly
+
+
+def edge_pair_batch(rng, n, tA, tB, cls, mesh_radii=None):
+    """pair_batch, then rewritten into one class of degenerate input (the same four arrays, float32 / int32):
+      coincident  both centres in one point (with a plane: the other body's centre in the plane's own point normal * offset);
+      deep        the second centre pulled towards the first by a uniform share (with a plane: the body pushed up to 1.5 below it);
+      far         both bodies moved by k * (1, 1, 1), k one of 1e3, 1e4, -3e3 (a plane's offset follows): an ulp of 1e-4 .. 1e-3;
+      scale       every length - extents, radii, half lengths, plane offset, positions - times 0.01 or 100 (not for polyhedra);
+      aspect      plates and needles: one half extent of a box 0.004 or 5, the half length of a capsule / cylinder 0.002 or 5
+                  (never 0: a capsule or cylinder without length is outside the reference's domain, oracle/README.md);
+      lattice     identity orientations, sizes and positions on a 0.25 grid, the plane y = 0: exact zeros of either sign and
+                  separations that equal a threshold of 0.25 exactly."""
+    CAP, CYL, POLY = getattr(scenes, "SHAPE_CAPSULE", 4), getattr(scenes, "SHAPE_CYLINDER", 5), getattr(scenes, "SHAPE_POLYHEDRON", 6)
+    st, sp, pos, orn = pair_batch(rng, n, tA, tB, mesh_radii)
+    types = (tA, tB)
+    plane = 0 if tA == scenes.SHAPE_PLANE else (1 if tB == scenes.SHAPE_PLANE else None)
+    body = None if plane is None else 1 - plane
+    if cls == "coincident":
+        if plane is None:
+            pos[:, 1] = pos[:, 0]
+        else:
+            pos[:, body] = sp[:, plane, :3] * sp[:, plane, 3:4]
+    elif cls == "deep":
+        if plane is None:
+            u = rng.random(n).astype(np.float32)
+            pos[:, 1] = pos[:, 0] + (pos[:, 1] - pos[:, 0]) * u[:, None]
+        else:
+            u = rng.uniform(0, 1.5, size=n).astype(np.float32)
+            pos[:, body] = pos[:, body] - sp[:, plane, :3] * u[:, None]
+    elif cls == "far":
+        k = rng.choice(np.float32([1e3, 1e4, -3e3]), size=n)
+        off = k[:, None] * np.ones(3, np.float32)
+        if plane is None:
+            pos[:, 0] += off; pos[:, 1] += off
+        else:
+            sp[:, plane, 3] += (sp[:, plane, :3] * off).sum(axis=1, dtype=np.float32)
+            pos[:, body] += off
+    elif cls == "scale":
+        assert POLY not in types, "a mesh has one size"
+        f = rng.choice(np.float32([0.01, 100]), size=n)
+        for side, t in enumerate(types):
+            if t == scenes.SHAPE_BOX:
+                sp[:, side, :3] *= f[:, None]
+            elif t == scenes.SHAPE_SPHERE:
+                sp[:, side, 0] *= f
+            elif t in (CAP, CYL):
+                sp[:, side, :2] *= f[:, None]
+            else:
+                sp[:, side, 3] *= f
+        pos *= f[:, None, None]
+    elif cls == "aspect":
+        for side, t in enumerate(types):
+            if t == scenes.SHAPE_BOX:
+                sp[np.arange(n), side, rng.integers(0, 3, n)] = rng.choice(np.float32([0.004, 5.0]), size=n)
+            elif t in (CAP, CYL):
+                sp[:, side, 1] = rng.choice(np.float32([0.002, 5.0]), size=n)
+    elif cls == "lattice":
+        orn[:] = (0, 0, 0, 1)
+        for side, t in enumerate(types):
+            if t == scenes.SHAPE_BOX:
+                sp[:, side, :3] = rng.choice(np.float32([0.25, 0.5, 1]), size=(n, 3))
+            elif t == scenes.SHAPE_SPHERE:
+                sp[:, side, 0] = rng.choice(np.float32([0.25, 0.5]), size=n)
+            elif t in (CAP, CYL):
+                sp[:, side, :2] = rng.choice(np.float32([0.25, 0.5]), size=(n, 2))
+            elif t == scenes.SHAPE_PLANE:
+                sp[:, side] = (0, 1, 0, 0)
+        # a mesh is smaller than the biggest grid shapes and has no size to draw: offsets of up to 6 cells leave under a tenth
+        # of the pairs with a polyhedron touching, 3 cells leave more than a fifth
+        reach = 3 if POLY in types else 6
+        pos[:, 0] = rng.integers(-4, 5, size=(n, 3)) * np.float32(0.25)
+        pos[:, 1] = pos[:, 0] + rng.integers(-reach, reach + 1, size=(n, 3)) * np.float32(0.25)
+        if plane is not None:
+            pos[:, plane] = 0
+    else:
+        raise ValueError(cls)
+    return st, sp.astype(np.float32), pos.astype(np.float32), orn.astype(np.float32)
