@@ -110,7 +110,7 @@ PATH_BITS = {"COMPACT_DIRECT": 1 << 0, "COMPACT_LIBRARY": 1 << 1, "SORT_DIRECT":
              "POS_COLOUR_PUSH": 1 << 18, "MIXED": 1 << 19, "ISLAND_FUSED": 1 << 20, "PER_COLOUR": 1 << 21, "POLY_ONE_LANE": 1 << 22,
              "POLY_AXES8": 1 << 23, "POLY_AXES16": 1 << 24, "POLY_CONTACTS4": 1 << 25, "POLY_CONTACTS8": 1 << 26,
              "POLY_CONTACTS16": 1 << 27, "POLY_HINTS": 1 << 28, "RECORDS_DIRECT": 1 << 29, "RECORDS_COPY": 1 << 30,
-             "WORLD_SERIAL": 1 << 31, "VEL_NAP": 1 << 32}
+             "WORLD_SERIAL": 1 << 31, "VEL_NAP": 1 << 32, "LISTS_KEPT": 1 << 33, "LISTS_MOVED": 1 << 34, "PAIR_SURPLUS": 1 << 35}
 
 # every symbol include/edynhip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_set_stream", "edynhip_set_bodies",

@@ -790,6 +790,9 @@ int broadphase(edynhip_ctx *c) {
         if (c->cnt_host->pair_overflow) return set_error(c, EDYNHIP_ERR_CAPACITY, c->cnt_host->pair_overflow == 2 ? "broadphase: BVH traversal stack exhausted" : "broadphase: pair capacity (max_manifolds) exceeded");
         if (c->cnt_host->df_abort) return set_error(c, EDYNHIP_ERR_INTERNAL, "dataflow solve: a hand-off never arrived in the previous step (workgroups not co-resident?)");
         M = c->cnt_host->num_pairs;
+        // (!force implies a full step) the lists this step's predicates ran over: an earlier step's, or rebuilt on the device's own flag
+        if (!force) c->paths |= c->cnt_host->bp_rebuilt ? EDYNHIP_PATH_LISTS_MOVED : EDYNHIP_PATH_LISTS_KEPT;
+        if (c->cnt_host->num_extra) c->paths |= EDYNHIP_PATH_PAIR_SURPLUS;
         {   // adapt the lists' look-ahead (ctx.hpp LBVH::lookahead): rebuilt in each of the last 4 steps -> halve; at most twice in the last 8 -> double
             const bool adapt = c->knobs.bp_adapt;   // developer knob (A/B)
             const bool rebuilt = force != 0 || c->cnt_host->bp_rebuilt != 0;

@@ -1973,20 +1973,40 @@ k_pos_contacts_tail(TailRanges tr, Rows rows, Manifolds mf, Bodies b, float *isl
     }
 }
 // The serial bucket (ctx.hpp kSerialColour): its manifolds may share bodies, so one lane (velocity) / one lane pair (position)
-// takes them one after the other, in sorted order; the fence makes each manifold's stores visible to the next one's loads.
+// takes them one after the other, in CANONICAL order (ascending manifold index, the checker's order); the fence makes each manifold's
+// stores visible to the next one's loads. A colour's sorted range is grouped by point count (4, 3, 2, 1) and ascending by manifold
+// inside a group, so the canonical order is a four-way merge of the groups (until the broadphase-edge tests the bucket was walked in
+// sorted order: right only while the groups of a bucket share no body - 65 coincident boxes and spheres were the first that did).
+struct SerialWalk { uint32_t cur[4], end[4]; };
+DI SerialWalk serial_walk(uint32_t start, uint32_t end, const Split &sp) {
+    const uint32_t e4 = min(max(sp.e4, start), end), e3 = min(max(sp.e3, e4), end), e2 = min(max(sp.e2, e3), end);
+    return SerialWalk{{start, e4, e3, e2}, {e4, e3, e2, end}};
+}
+DI uint32_t serial_next(SerialWalk &w, const uint32_t *order) {   // the sorted position of the lowest manifold not taken yet (the caller counts end - start calls)
+    uint32_t best = 0xFFFFFFFFu, g_best = 0;
+#pragma unroll
+    for (uint32_t g = 0; g < 4; ++g) {
+        if (w.cur[g] < w.end[g]) { const uint32_t m = order[w.cur[g]]; if (m < best) { best = m; g_best = g; } }
+    }
+    return w.cur[g_best]++;
+}
 template <bool WARM, bool FUSED>
 __global__ void __launch_bounds__(64)
-k_contact_solve_serial(uint32_t start, uint32_t end, Split sp, const uint32_t *rbA, const uint32_t *rbB, float4 *rw, uint32_t rcap, float4 *bdvw, float4 *rwx) {
+k_contact_solve_serial(uint32_t start, uint32_t end, Split sp, const uint32_t *order, const uint32_t *rbA, const uint32_t *rbB, float4 *rw, uint32_t rcap, float4 *bdvw, float4 *rwx) {
     if (threadIdx.x != 0) return;
-    for (uint32_t p = start; p < end; ++p) {
+    SerialWalk w = serial_walk(start, end, sp);
+    for (uint32_t k = start; k < end; ++k) {
+        const uint32_t p = serial_next(w, order);
         contact_solve_lane<WARM, false, FUSED>(p, np_of(p, sp), rbA, rbB, rw, rcap, bdvw, nullptr, rwx);
         __threadfence();
     }
 }
 template <bool BLOCK>
 __global__ void __launch_bounds__(64)
-k_pos_contacts_serial(uint32_t start, uint32_t end, Rows rows, Manifolds mf, Bodies b, float *isl_err, const uint32_t *isl_done) {
-    for (uint32_t p = start; p < end; ++p) {
+k_pos_contacts_serial(uint32_t start, uint32_t end, Split sp, Rows rows, Manifolds mf, Bodies b, float *isl_err, const uint32_t *isl_done) {
+    SerialWalk w = serial_walk(start, end, sp);   // (every lane walks the same merge: p is uniform)
+    for (uint32_t k = start; k < end; ++k) {
+        const uint32_t p = serial_next(w, rows.order);
         pos_contacts_lane<BLOCK>(p, p + 1, threadIdx.x, rows, mf, b, isl_err, isl_done);
         __threadfence();
     }
@@ -2693,7 +2713,7 @@ static void rec(edynhip_ctx *c, int idx) {
 // by default, EDYNHIP_FLAG_FUSED_VELOCITY_ROWS / EDYNHIP_FLAG_BLOCK_POSITION opt in to the coloured order's own forms).
 using ContactSolveFn = void (*)(uint32_t, uint32_t, Split, const uint32_t *, const uint32_t *, float4 *, uint32_t, float4 *, const float *, float4 *);
 using ContactTailFn = void (*)(TailRanges, const uint32_t *, const uint32_t *, float4 *, uint32_t, float4 *, const float *, float4 *);
-using ContactSerialFn = void (*)(uint32_t, uint32_t, Split, const uint32_t *, const uint32_t *, float4 *, uint32_t, float4 *, float4 *);
+using ContactSerialFn = void (*)(uint32_t, uint32_t, Split, const uint32_t *, const uint32_t *, const uint32_t *, float4 *, uint32_t, float4 *, float4 *);
 static ContactSolveFn contact_solve_fn(bool warm, bool push, bool fused) {
     static const ContactSolveFn t[2][2][2] = {{{k_contact_solve<false, false, false>, k_contact_solve<false, false, true>}, {k_contact_solve<false, true, false>, k_contact_solve<false, true, true>}},
                                               {{k_contact_solve<true, false, false>, k_contact_solve<true, false, true>}, {k_contact_solve<true, true, false>, k_contact_solve<true, true, true>}}};
@@ -2979,7 +2999,7 @@ static void contacts_pass(edynhip_ctx *c, const SolvePlan &p, bool warm, uint32_
     if (p.serial) {
         const uint32_t a = c->colour_start[kSerialColour], e = c->colour_end[kSerialColour];
         const Split sp{c->colour_split[kSerialColour][0], c->colour_split[kSerialColour][1], c->colour_split[kSerialColour][2]};
-        hipLaunchKernelGGL(contact_serial_fn(warm, fused_rows), dim3(1), dim3(64), 0, s, a, e, sp, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, c->extras ? r.rwx : (float4 *)nullptr);
+        hipLaunchKernelGGL(contact_serial_fn(warm, fused_rows), dim3(1), dim3(64), 0, s, a, e, sp, (const uint32_t *)r.order, (const uint32_t *)r.bA, (const uint32_t *)r.bB, r.rw, rcap, c->b.dvw, c->extras ? r.rwx : (float4 *)nullptr);
         ++*launches;
     }
 }
@@ -3059,7 +3079,7 @@ static void pos_per_colour(edynhip_ctx *c, const SolvePlan &p, uint32_t first_it
             if (e > a) hipLaunchKernelGGL(block_pos ? k_pos_contacts<true> : k_pos_contacts<false>, dim3(blocks(2 * (e - a), 128)), dim3(128), 0, s, a, e, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
         }
         if (p.tail.n) hipLaunchKernelGGL(block_pos ? k_pos_contacts_tail<true> : k_pos_contacts_tail<false>, dim3(1), dim3(256), 0, s, p.tail, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
-        if (p.serial) hipLaunchKernelGGL(block_pos ? k_pos_contacts_serial<true> : k_pos_contacts_serial<false>, dim3(1), dim3(64), 0, s, c->colour_start[kSerialColour], c->colour_end[kSerialColour], c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
+        if (p.serial) hipLaunchKernelGGL(block_pos ? k_pos_contacts_serial<true> : k_pos_contacts_serial<false>, dim3(1), dim3(64), 0, s, c->colour_start[kSerialColour], c->colour_end[kSerialColour], Split{c->colour_split[kSerialColour][0], c->colour_split[kSerialColour][1], c->colour_split[kSerialColour][2]}, c->rows, mf, c->b, c->isl_err, (const uint32_t *)c->isl_done);
         hipLaunchKernelGGL(k_pos_flags, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->isl_err, c->isl_done);
     }
 }

@@ -519,6 +519,9 @@ int edynhip_debug_collide(edynhip_ctx *ctx, uint32_t n, const int32_t *shape_typ
 #define EDYNHIP_PATH_RECORDS_COPY       (1ull << 30)  /* ... through a device block and the copy engine */
 #define EDYNHIP_PATH_WORLD_SERIAL       (1ull << 31)  /* multi-device world only: the shards were stepped on the caller's thread */
 #define EDYNHIP_PATH_VEL_NAP            (1ull << 32)  /* k_contact_solve_df2 launched with a pause between polls other than the default (EDYNHIP_DF_NAP) */
+#define EDYNHIP_PATH_LISTS_KEPT         (1ull << 33)  /* a full step ran the exact predicates over candidate lists built in an earlier step */
+#define EDYNHIP_PATH_LISTS_MOVED        (1ull << 34)  /* a full step rebuilt the candidate lists on the device's own flag (a body left its slack) */
+#define EDYNHIP_PATH_PAIR_SURPLUS       (1ull << 35)  /* some owner reported pairs through the unsorted surplus (more than 64 partners, or a sleeping owner): the surplus sort ran */
 int edynhip_debug_paths(edynhip_ctx *ctx, uint64_t *mask);
 
 /* Island sleeping (EDYNHIP_FLAG_SLEEPING): asleep[n] = 1 where the body carries sleeping_tag; wake_all = wake_up_entity on

@@ -45,6 +45,7 @@ import edyn_amd
 from edyn_amd import scenes
 from edyn_amd._capi import PATH_BITS
 from oracle import binding as ob
+import bplayouts
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -165,6 +166,10 @@ SCENES = {
     "pile_and_ragdolls": dict(make=_pile_and_ragdolls, figures=True),
     "ragdolls": dict(make=lambda: scenes.figures(scenes.load_figure(os.path.join(GOLDEN, "ragdoll_capsule.npz")), 2, 2, pitch=1.6), figures=True),   # small islands, all with joints
     "polyheap5": dict(make=lambda: scenes.polyhedron_heap(5, 5, 5)),
+    # layouts of tests/bplayouts.py (held to the oracle at length in test_broadphase_edges.py): spheres in flight, whose candidate lists
+    # are reused for a few steps and then expire on the device's own flag; an owner of 65 partners, one more than a lane group keeps
+    "gas": dict(make=lambda: bplayouts.gas(bplayouts.GAS_CENTRES["origin"])),
+    "owner65": dict(make=lambda: bplayouts.owner_k(65, speed=0.05)),
     # not stepped against the oracle's world: see _run_collide, _run_records, _run_world
     "collide_poly_poly": dict(kind="collide", shapes=(scenes.SHAPE_POLYHEDRON, scenes.SHAPE_POLYHEDRON)),
     "collide_poly_box": dict(kind="collide", shapes=(scenes.SHAPE_POLYHEDRON, scenes.SHAPE_BOX), inert=True),   # inert: the knob must select nothing here
@@ -193,6 +198,8 @@ MATRIX = [
     ({}, "pile_and_ragdolls", 30, {"=MIXED", "=PER_COLOUR"}, set()),
     ({}, "ragdolls", 30, {"=ISLAND_FUSED"}, {"MIXED", "VEL_LANES1", "VEL_LANES2", "VEL_LANES4"}),
     ({}, "polyheap5", 60, {"=POLY_AXES8", "=POLY_CONTACTS4", "=POLY_HINTS"}, {"POLY_ONE_LANE", "POLY_AXES16", "POLY_CONTACTS8", "POLY_CONTACTS16"}),
+    ({}, "gas", 20, {"=LISTS_KEPT", "=LISTS_MOVED"}, {"PAIR_SURPLUS", "LISTS_FORCED"}),
+    ({}, "owner65", 10, {"=PAIR_SURPLUS", "=LISTS_KEPT"}, {"LISTS_FORCED"}),
     # ---- dataflow solve
     ({"EDYNHIP_DATAFLOW_POS": "0"}, "mixed6", 60, {"POS_COLOUR_PUSH", "=VEL_LANES2"}, {"POS_MULTI_ROUND", "PER_COLOUR"}),
     ({"EDYNHIP_DATAFLOW_POS": "0"}, "mixed6_fused_arith", 60, {"POS_COLOUR_PUSH"}, set()),
@@ -210,7 +217,7 @@ MATRIX = [
     # ---- broadphase and manifold build: collapsing pile ...
     ({"EDYNHIP_SPECULATE": "0"}, "mixed5", 60, set(), {"SPECULATE"}),
     ({"EDYNHIP_INPLACE": "0"}, "mixed5", 60, set(), {"INPLACE"}),
-    ({"EDYNHIP_BP_LISTS": "0"}, "mixed5", 60, {"LISTS_FORCED"}, set()),
+    ({"EDYNHIP_BP_LISTS": "0"}, "mixed5", 60, {"LISTS_FORCED"}, {"LISTS_KEPT", "LISTS_MOVED"}),
     ({"EDYNHIP_BP_ADAPT": "0"}, "mixed5", 60, set(), {"LOOKAHEAD_CHANGED"}),   # (inert here: INERT_ROWS)
     ({"EDYNHIP_DIRECT_COMPACT": "0"}, "mixed5", 60, {"COMPACT_LIBRARY"}, {"COMPACT_DIRECT"}),
     (BP_ALL_OFF, "mixed5", 60, {"LISTS_FORCED", "COMPACT_LIBRARY"}, {"SPECULATE", "COMPACT_DIRECT", "INPLACE", "LOOKAHEAD_CHANGED"}),

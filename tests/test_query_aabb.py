@@ -13,6 +13,7 @@ import edyn_amd
 from edyn_amd import _capi, scenes
 from edyn_amd.world import EdynHipError
 
+import bplayouts as bl
 import query_ref
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
@@ -132,6 +133,34 @@ def test_tree_equals_brute_force_equals_definition(name):
     assert counts[:6].min() == _masks(scene["kind"], scene["shape_type"])["procedural"].sum()   # the huge queries report every body
     assert (counts[6:12] == 0).all() and (counts[12:18] == 0).all()                             # empty and NaN queries nothing
     assert (counts > 32).sum() > 100 and ((counts > 0) & (counts <= 32)).sum() > 100
+
+
+# Layouts the Morton stage and the Karras build never see in a pile (tests/bplayouts.py): no extent on one, two or all axes, runs of equal
+# codes, everyone but an outlier in one cell, a body that contains the scene, and trees of one, two and three leaves (with and without
+# static bodies, the other category's tree).
+LAYOUTS = {"coincident200": lambda: bl.coincident(200), "line": bl.line, "clusters": bl.clusters, "outlier-first": lambda: bl.outlier(True),
+           "outlier-last": lambda: bl.outlier(False), "giant-first": lambda: bl.giant("first"), "giant-static": lambda: bl.giant("static"),
+           "counts1": lambda: bl.counts(1, 1), "counts2": lambda: bl.counts(2), "counts3": lambda: bl.counts(3, 4), "counts257": lambda: bl.counts(257, 5)}
+
+
+@pytest.mark.parametrize("name", list(LAYOUTS))
+def test_tree_equals_brute_force_equals_definition_on_degenerate_layouts(name):
+    """5 000 query boxes of _queries' mix, drawn about the bulk of the scene (the bodies within its 2nd to 98th percentile, so that an
+    outlier does not dilute them; the huge, touching and twin queries still reach every body): tree == brute force == definition."""
+    scene = LAYOUTS[name]()
+    w = _world(scene)
+    w.refresh_derived()
+    aabb = w.get_derived()[0]
+    lo, hi = np.percentile(aabb[:, :3], 2, axis=0), np.percentile(aabb[:, 3:], 98, axis=0)
+    bulk = np.all((aabb[:, :3] >= lo - 1) & (aabb[:, 3:] <= hi + 1), axis=1)
+    q = _queries(aabb[bulk], 5000 - 12, 17)
+    ends = np.concatenate([aabb[:6], aabb[-6:]])   # the first and the last bodies' own boxes, wherever they are
+    q = np.concatenate([q, ends]).astype(np.float32)
+    res = _check(w, scene["kind"], scene["shape_type"], q, name)
+    counts = np.diff(res["procedural"][0][0].astype(np.int64))
+    nproc = int(_masks(scene["kind"], scene["shape_type"])["procedural"].sum())
+    assert counts[:6].min() == nproc   # the huge queries report every body, the one at 1e6 and the one of radius 500 included
+    assert (counts[6:12] == 0).all() and (counts[12:18] == 0).all()
 
 
 def test_sleepers_removed_added_moved_bodies():

@@ -7,6 +7,7 @@ import pytest
 import edyn_amd
 from edyn_amd import _capi, scenes
 
+import bplayouts as bl
 import raycast_ref
 
 pytestmark = pytest.mark.gpu
@@ -167,6 +168,34 @@ def test_tree_equals_brute_force(name):
     brute = w.raycast(p0, p1, brute_force=True)
     _assert_same(tree, brute, name)
     assert (tree["body"] != NONE).mean() > 0.2
+
+
+# Layouts the Morton stage and the Karras build never see in a pile (tests/bplayouts.py): no extent on one, two or all axes, runs of equal
+# codes, everyone but an outlier in one cell, a body that contains the scene, and trees of one, two and three leaves.
+LAYOUTS = {"coincident200": lambda: bl.coincident(200), "line": bl.line, "clusters": bl.clusters, "outlier-first": lambda: bl.outlier(True),
+           "outlier-last": lambda: bl.outlier(False), "giant-first": lambda: bl.giant("first"), "giant-static": lambda: bl.giant("static"),
+           "counts1": lambda: bl.counts(1), "counts2": lambda: bl.counts(2), "counts3": lambda: bl.counts(3), "counts257": lambda: bl.counts(257, 4)}
+
+
+@pytest.mark.parametrize("name", list(LAYOUTS))
+def test_tree_equals_brute_force_on_degenerate_layouts(name):
+    """15 000 random rays about the bulk of the scene (its 2nd to 98th percentile, so that an outlier does not dilute them), 5 000 along
+    the faces of the candidate boxes, and 100 aimed at the centres of the first and the last body from afar: tree == brute force."""
+    scene = LAYOUTS[name]()
+    w = _world(scene)
+    w.refresh_derived()
+    aabb, _, _ = w.get_derived()
+    lo, hi = np.percentile(aabb[:, :3], 2, axis=0), np.percentile(aabb[:, 3:], 98, axis=0)
+    p0, p1 = _random_rays(15000, lo - 2, hi + 2, 7)
+    g0, g1 = _grazing_rays(aabb, 5000, 8)
+    a0, _ = _random_rays(100, lo - 2, hi + 2, 9)
+    ends = scene["pos"][np.where(np.arange(100) & 1, len(aabb) - 1, 0)]
+    a1 = (ends + (ends - a0) * np.float32(0.01)).astype(np.float32)   # a little beyond the centre
+    p0, p1 = np.concatenate([p0, g0, a0]), np.concatenate([p1, g1, a1])
+    tree = w.raycast(p0, p1)
+    brute = w.raycast(p0, p1, brute_force=True)
+    _assert_same(tree, brute, name)
+    assert (tree["body"] != NONE).any()
 
 
 def _reference_best(ref, scene, pos, orn, aabb, com, p0, p1):
