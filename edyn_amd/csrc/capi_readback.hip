@@ -157,7 +157,7 @@ int edynhip_set_state(edynhip_ctx *c, const float *pos, const float *orn, const 
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the staging buffers are reused by the next call
     if (e != hipSuccess) return set_error(c, EDYNHIP_ERR_HIP, "edynhip_set_state", e);
     invalidate_bodies_moved(c);   // moved behind the broadphase's back: the candidate lists are rebuilt at the next step
-    // (The AABBs stay those of the old state until the end of the next step. edynhip_world_set_state in multi.hip relies on it: it runs
+    // (The AABBs stay those of the old state until the end of the next step. edynhip_world_set_state in multi_edit.hip relies on it: it runs
     // its approach check AFTER that step, when the boxes - and the first new pairs - can first exist. Refreshing the boxes here would
     // need the check before the step there.)
     if (c->sleeping) return edynhip_wake_all(c);   // an edited body wakes its island (wake_up_entity); all of them here

@@ -519,15 +519,15 @@ struct edynhip_ctx {
     uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
     eh::RayTree *ray = nullptr;
     eh::QueryAabb *qa = nullptr;   // AABB queries (query_aabb.hip): counts, scan and island boxes beside the raycast's tree
-    bool world_shard = false;      // a shard of a multi-device world (multi.hip): the public queries are refused, the world asks through shard_*
-    // Queries on a multi-device world (multi.hip edynhip_world_raycast / edynhip_world_query_aabb): every body is answered by exactly one
+    bool world_shard = false;      // a shard of a multi-device world (multi.hpp): the public queries are refused, the world asks through shard_*
+    // Queries on a multi-device world (multi_query.hip edynhip_world_raycast / edynhip_world_query_aabb): every body is answered by exactly one
     // shard. answers: device bit per local body this context answers for (nullptr: all of them), host_answers its host copy (empty: all);
     // query_island: island labels carried through a re-partition, read by the island category until this context's first step recomputes
     // b.island. The device arrays are the world's (Shard), set by eh::shard_set_answers.
     const uint32_t *answers = nullptr;
     std::vector<uint32_t> host_answers;
     const uint32_t *query_island = nullptr;
-    // Contact events of a shard (multi.hip build_shard; both 0 on a context of its own): events carry event_step_base + step_index - the
+    // Contact events of a shard (multi_shard.hip build_shard; both 0 on a context of its own): events carry event_step_base + step_index - the
     // world's step count, which goes on where a re-partition restarts step_index - and every point id issued here has event_id_tag (the
     // shard, above the manifold index: kEventTagShift) in its low word, so that ids of different shards never collide.
     uint32_t event_step_base = 0, event_id_tag = 0;

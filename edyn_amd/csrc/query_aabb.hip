@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(256) k_qa_scan_fill(QaArgs a, const float4 *__
     if (lane == 0 && done) atomicAdd(stats + 1, (unsigned long long)done);   // edynhip_query_aabb_stats: queries a wave packed
 }
 
-// ---- islands: segmented min / max of the query tree's per-body boxes by island label (multi.hip k_island_box_* on Bodies::amin / amax)
+// ---- islands: segmented min / max of the query tree's per-body boxes by island label (multi_partition.hip k_island_box_* on Bodies::amin / amax)
 DI uint32_t qa_ordered(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 DI float qa_unordered(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 __global__ void k_qa_isl_clear(uint32_t n, uint32_t *lo, uint32_t *hi, uint32_t *flag) {

@@ -320,7 +320,7 @@ int shard_raycast(edynhip_ctx *c, uint32_t n, const void *p0_f4, const void *p1_
 
 using namespace eh;
 // Unknown flag bits and shard contexts (edynhip_world_context) are rejected: a world asks its shards through eh::shard_raycast
-// (edynhip_world_raycast, multi.hip).
+// (edynhip_world_raycast, multi_query.hip).
 static int check_call(edynhip_ctx *c, uint32_t flags, const char *who) {
     if (flags & ~(uint32_t)EDYNHIP_RAYCAST_BRUTE_FORCE) return set_error(c, EDYNHIP_ERR_INVALID, (std::string(who) + ": unknown flag bits").c_str());
     if (c->world_shard) return set_error(c, EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": a shard of a multi-device world has no raycast").c_str());

@@ -1,4 +1,4 @@
-// Queries on a multi-device world (multi.hip edynhip_world_raycast / edynhip_world_query_aabb): what runs beside the shards' own
+// Queries on a multi-device world (multi_query.hip edynhip_world_raycast / edynhip_world_query_aabb): what runs beside the shards' own
 // kernels - index translation on a shard's device, and the merges on the world's home device (world_query.hip).
 #pragma once
 #include <hip/hip_runtime.h>

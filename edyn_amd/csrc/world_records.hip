@@ -1,4 +1,4 @@
-// Record hand-over of a multi-device world (multi.hip edynhip_world_snapshot_records / edynhip_world_snapshot_map): what a shard context
+// Record hand-over of a multi-device world (multi_records.hip edynhip_world_snapshot_records / edynhip_world_snapshot_map): what a shard context
 // does for it. Every shard packs the 96-byte registry records (edynhip_body_record) of the bodies it reports - its own dynamic bodies,
 // shard 0 also the replicated ones: the context's `answers` bits - with the single context's record arithmetic (drecord.hpp body_record)
 // and stores them at the bodies' GLOBAL indices straight into the world's pinned slot, which is mapped into every shard's device. No

@@ -1,4 +1,4 @@
-// The host rules of the multi-device world (multi.hip), each written once: which island a body belongs to before a device has said
+// The host rules of the multi-device world (multi.hpp, multi*.hip), each written once: which island a body belongs to before a device has said
 // so, which shard an island, a body, a joint or an exclusion pair lives on, and when a partition is given up for a balanced one.
 // Pure functions over arrays and small structs - no HIP, no context, no world - so every rule is tested on a machine without a GPU
 // (tests/cpp/world_rules.cpp; the partitioner and the box sweep also through the C-ABI, tests/test_partition.py).

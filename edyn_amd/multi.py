@@ -1,4 +1,4 @@
-"""MultiWorld: thin binding of the library's multi-GPU world (include/edynhip.h "Multi-GPU world", edyn_amd/csrc/multi.hip).
+"""MultiWorld: thin binding of the library's multi-GPU world (include/edynhip.h "Multi-GPU world", edyn_amd/csrc/multi*.hip).
 
 One simulation, several GPUs of one node, one process: every device steps the islands it owns (solver.cpp:408-428: the island is
 the reference's own unit of parallelism), the library gathers the state after every step, watches island bounding boxes reduced on

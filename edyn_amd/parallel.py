@@ -77,7 +77,7 @@ def partition_islands(labels, kind, weights, world_size):
     weights [n] per-body cost (e.g. contact points the body takes part in; 1 = balance body counts)
     Deterministic: islands by descending weight, ties by ascending label, each to the currently lightest rank (ties to
     the lowest rank) - longest-processing-time-first. Returns rank_of_body [n] (-1 = replicated).
-    The partitioner itself is the library's (edynhip_partition_islands, edyn_amd/csrc/multi.hip - host code, no GPU needed):
+    The partitioner itself is the library's (edynhip_partition_islands, edyn_amd/csrc/multi_partition.hip - host code, no GPU needed):
     the single-process multi-GPU world (edynhip_world_*) and this multi-process one partition alike."""
     from . import _capi
     labels = np.ascontiguousarray(labels, np.uint32); kind = np.ascontiguousarray(kind, np.int32)

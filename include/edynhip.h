@@ -589,7 +589,7 @@ int edynhip_measure_bandwidth(edynhip_ctx *ctx, uint64_t bytes, float *read_gbs,
  * body; shards step concurrently (one private host thread each) with NO exchange inside a step; after each step the integrated
  * state of every shard is copied into pinned host memory and from there into the world's arrays (edynhip_world_get_state); the
  * registry write-back reads edynhip_world_snapshot_records' records in place (below). Islands of different shards that approach each other are noticed from island bounding boxes reduced ON
- * THE DEVICE (edyn_amd/csrc/multi.hip), and the world re-partitions, carrying contact manifolds (warm-start impulses, colours),
+ * THE DEVICE (edyn_amd/csrc/multi_partition.hip), and the world re-partitions, carrying contact manifolds (warm-start impulses, colours),
  * joint impulses / angles, sleeping tags, exclusions, joint definitions and meshes to the islands' new owners. A shard computes
  * for its islands bit for bit what one context computes for the whole world (tests/cpp/multi.cpp).
  * Body / joint indices of this interface are GLOBAL (the caller's order). `devices` may name a device more than once (several

@@ -1,4 +1,4 @@
-// The multi-GPU world of the C-ABI (include/edynhip.h "Multi-GPU world", edyn_amd/csrc/multi.hip) next to ONE context stepping the
+// The multi-GPU world of the C-ABI (include/edynhip.h "Multi-GPU world", edyn_amd/csrc/multi*.hip) next to ONE context stepping the
 // same scene: six mini-piles (six islands) and a sphere that rolls from the first pile into the fourth - its island meets an
 // island that lives on the other shard, which forces a re-partition with the contact manifolds carried along; later a forced
 // re-partition. Positions, orientations and velocities must be bit-equal after every step. Two shards on one physical GPU

@@ -22,7 +22,7 @@ def test_sharded_hip_worlds_match_the_unsharded_gpu_world(tmp_path):
     assert np.array_equal(got["states"], ref)
 
 
-# ---- the multi-GPU world BEHIND the C-ABI (edynhip_world_*, edyn_amd/csrc/multi.hip) ----------------------
+# ---- the multi-GPU world BEHIND the C-ABI (edynhip_world_*, edyn_amd/csrc/multi*.hip) ----------------------
 # Two shards on the one physical GPU of the test box: one process, one host thread per shard, island boxes reduced on the device,
 # re-partitions inside edynhip_world_step. The trajectory must equal ONE context stepping the whole scene, bit for bit.
 def _single_world_states(scene, steps):

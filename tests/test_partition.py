@@ -1,5 +1,5 @@
 """The island partitioner and the island-box sweep of the library (edynhip_partition_islands, edynhip_island_boxes_overlap:
-host rules of edyn_amd/csrc/world_rules.hpp behind the entry points of multi.hip, shared by the single-process multi-GPU world and by
+host rules of edyn_amd/csrc/world_rules.hpp behind the entry points of multi_partition.hip, shared by the single-process multi-GPU world and by
 ShardedWorld) - no GPU needed. The world's other host rules are checked by tests/test_world_rules.py.
 Checked against plain numpy restatements of the same rules, at world sizes up to 8."""
 import numpy as np

@@ -285,6 +285,33 @@ def test_a_view_stays_valid_until_the_next_but_one_snapshot(shards):
     mw.close()
 
 
+def _state_after_five_steps():
+    mw = _world(2)
+    mw.step_simulation(5)
+    state = b"".join(np.ascontiguousarray(a).tobytes() for a in mw.get_state())
+    mw.close()
+    return state
+
+
+def test_destroy_before_the_build_and_with_a_pack_pending():
+    """The two ways out of a world that no other test takes: destroyed as described, before any shard exists, and destroyed right behind a
+    snapshot nobody mapped, while the shards' packs into the pinned slot may still be running. Both return quietly and leave the device as
+    a process that never did either finds it: a world made afterwards steps to the state a fresh process computes (this file run as a
+    script)."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    fresh = subprocess.run([sys.executable, os.path.abspath(__file__)], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert fresh.returncode == 0, fresh.stderr[-2000:]
+    mw = _world(2, contact_events=True)
+    mw.close()                                                                    # described, never built
+    mw = _world(2, contact_events=True)
+    mw.step_simulation(5)
+    mw.snapshot_records(0.004, 4096)
+    mw.close()                                                                    # both shards' packs and the event block are out
+    assert _state_after_five_steps().hex() == fresh.stdout.strip()
+
+
 def test_arguments():
     L = _capi.lib()
     mw = _world(2, contact_events=True)
@@ -305,3 +332,7 @@ def test_arguments():
 
 def _capi_direct():
     return 1   # EDYNHIP_SNAPSHOT_DIRECT
+
+
+if __name__ == "__main__":   # the fresh process of test_destroy_before_the_build_and_with_a_pack_pending
+    print(_state_after_five_steps().hex())
