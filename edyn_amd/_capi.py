@@ -96,6 +96,12 @@ RAYCAST_BRUTE_FORCE = 1   # EDYNHIP_RAYCAST_BRUTE_FORCE (test aid: every ray tes
 QUERY_PROCEDURAL, QUERY_NON_PROCEDURAL, QUERY_ISLANDS = 0, 1, 2   # EDYNHIP_QUERY_* categories of edynhip_query_aabb
 QUERY_CATEGORIES = {"procedural": QUERY_PROCEDURAL, "non_procedural": QUERY_NON_PROCEDURAL, "islands": QUERY_ISLANDS}
 QUERY_BRUTE_FORCE = 1     # EDYNHIP_QUERY_BRUTE_FORCE (test aid: every query tests every body / island)
+QUERY_TICKETS_MAX = 8     # EDYNHIP_QUERY_TICKETS_MAX: tickets outstanding at once (edynhip_raycast_submit / edynhip_query_aabb_submit)
+WANT_PROCEDURAL, WANT_NON_PROCEDURAL, WANT_ISLANDS, WANT_OF_INTEREST = 1, 2, 4, 8   # EDYNHIP_WANT_*: the lists a box of a ticket asks for
+
+
+class QueryAabbView(C.Structure):   # edynhip_query_aabb_view: a box ticket's lists, in pinned memory of the context
+    _fields_ = [("n", C.c_uint32), ("offsets", C.POINTER(C.c_uint32)), ("ids", C.POINTER(C.c_uint32)), ("total", C.c_uint64)]
 
 
 class RecordView(C.Structure):
@@ -134,6 +140,9 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_world_set_pair_filter", "edynhip_world_default_should_collide", "edynhip_get_sleep_timers", "edynhip_set_sleep_timers",
            "edynhip_raycast", "edynhip_raycast_device",
            "edynhip_query_aabb", "edynhip_query_aabb_device", "edynhip_query_aabb_stats",
+           # queries as tickets
+           "edynhip_raycast_submit", "edynhip_query_aabb_submit", "edynhip_query_poll", "edynhip_raycast_collect",
+           "edynhip_query_aabb_collect", "edynhip_query_release",
            "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device",
            "edynhip_world_get_contact_events", "edynhip_world_get_point_ids",
            "edynhip_debug_paths", "edynhip_world_debug_paths",
@@ -176,6 +185,12 @@ def lib():
         L.edynhip_query_aabb_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]
         L.edynhip_query_aabb_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.edynhip_raycast_submit.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.edynhip_query_aabb_submit.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.edynhip_query_poll.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int)]
+        L.edynhip_raycast_collect.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.edynhip_query_aabb_collect.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(QueryAabbView)]
+        L.edynhip_query_release.argtypes = [C.c_void_p, C.c_uint64]
         L.edynhip_num_manifolds.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.edynhip_get_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_set_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]

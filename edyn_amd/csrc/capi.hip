@@ -321,6 +321,7 @@ void edynhip_destroy(edynhip_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     eh::raycast_free(c);
     eh::query_aabb_free(c);
+    eh::query_tickets_free(c);
     c->allocs.insert(c->allocs.end(), c->mesh_allocs.begin(), c->mesh_allocs.end());   // what mesh.hip allocated for this context joins the arena
     c->allocs.push_back(c->rot); c->allocs.push_back(c->poly_work);
     for (void *p : c->allocs) (void)hipFree(p);

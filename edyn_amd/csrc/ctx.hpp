@@ -245,6 +245,7 @@ struct Knobs {
 
 struct RayTree;   // raytree.hpp (raycast.hip, query_aabb.hip)
 struct QueryAabb;   // query_aabb.hip
+struct QueryTickets;   // query_async.hip
 
 struct LBVH {
     uint64_t *keys = nullptr, *keys_sorted = nullptr;   // morton<<32 | body
@@ -519,6 +520,7 @@ struct edynhip_ctx {
     uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
     eh::RayTree *ray = nullptr;
     eh::QueryAabb *qa = nullptr;   // AABB queries (query_aabb.hip): counts, scan and island boxes beside the raycast's tree
+    eh::QueryTickets *qt = nullptr;   // ticketed queries (query_async.hip): the table of outstanding tickets and each slot's own buffers
     bool world_shard = false;      // a shard of a multi-device world (multi.hpp): the public queries are refused, the world asks through shard_*
     // Queries on a multi-device world (multi_query.hip edynhip_world_raycast / edynhip_world_query_aabb): every body is answered by exactly one
     // shard. answers: device bit per local body this context answers for (nullptr: all of them), host_answers its host copy (empty: all);
@@ -604,6 +606,7 @@ int build_query_tree(edynhip_ctx *c, const uint32_t *list, uint32_t n, const flo
                      uint64_t *keys, uint64_t *keys_sorted, uint32_t *parent, uint32_t *left, uint32_t *right, uint32_t *visit, uint32_t *rope);
 void raycast_free(edynhip_ctx *c);   // raycast.hip
 void query_aabb_free(edynhip_ctx *c);   // query_aabb.hip
+void query_tickets_free(edynhip_ctx *c);   // query_async.hip
 // what a multi-device world asks of a shard context (the public entry points refuse one): device arrays on the context's device, local
 // body indices, everything enqueued on the context's stream
 void shard_set_answers(edynhip_ctx *c, const uint32_t *answers_dev, std::vector<uint32_t> host_bits, const uint32_t *query_island_dev);

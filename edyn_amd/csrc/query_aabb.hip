@@ -89,12 +89,7 @@ struct QaArgs {
     uint32_t category, mode, scan_ratio;
 };
 
-// intersect_aabb(q.min, q.max, box.min, box.max), geom.cpp:762-770: the six comparisons as written.
-DI bool qa_overlap(f3 qmn, f3 qmx, f3 bmn, f3 bmx) {
-    return (qmn.x <= bmx.x) && (qmx.x >= bmn.x) && (qmn.y <= bmx.y) && (qmx.y >= bmn.y) && (qmn.z <= bmx.z) && (qmx.z >= bmn.z);
-}
-DI f3 qa_fat_min(float4 a) { return mk3(a.x - kFatInset, a.y - kFatInset, a.z - kFatInset); }
-DI f3 qa_fat_max(float4 a) { return mk3(a.x + kFatInset, a.y + kFatInset, a.z + kFatInset); }
+// (qa_overlap, qa_fat_min, qa_fat_max: raytree.hpp - the of-interest pass of query_async.hip runs the same test)
 // procedural: shaped, not removed, dynamic (capi.hip rebuild_broadphase_lists); non-procedural: shaped, not removed, static or kinematic
 DI bool qa_category(const QaArgs &a, uint32_t body) {
     if (a.answers && !((a.answers[body >> 5] >> (body & 31u)) & 1u)) return false;   // another shard's to answer
@@ -458,6 +453,70 @@ int shard_query_fill(edynhip_ctx *c, int category, uint32_t n, const void *boxes
     EH_HIP(c, hipSetDevice(c->device));
     QueryAabb &q = *c->qa;
     return run_query(c, category, n, (const float4 *)boxes_f4, flags, q.d_off, ids, capacity, q.d_total, false, true);
+}
+
+// ---- a box ticket (query_async.hip): the kernels above on the ticket's own buffers. Of the context's QueryAabb only what lives inside
+// one enqueue (the scan's block sums) or is keyed by state_epoch (the island boxes) is used: not cnt, mid, big, ctl[0..1], d_* or the
+// `counted` cache, which belong to the synchronous entry points.
+static QaArgs ticket_args(edynhip_ctx *c, int category, uint32_t flags) {
+    const QueryAabb &q = *c->qa;
+    const RayTree &t = *c->ray;
+    QaArgs a;
+    a.flags = c->b.flags; a.amin = t.amin; a.amax = t.amax; a.nmin = t.nmin; a.nmax = t.nmax; a.n_tree = t.n_tree;
+    a.planes = t.list + t.n_tree; a.n_planes = t.n_planes; a.n_bodies = c->b.n;
+    a.imin = q.imin; a.imax = q.imax; a.n_islands = q.ctl + 2; a.answers = c->answers;
+    a.category = (uint32_t)category; a.scan_ratio = q.scan_ratio;
+    a.mode = category == EDYNHIP_QUERY_ISLANDS ? QA_ISLANDS : (flags & EDYNHIP_QUERY_BRUTE_FORCE) ? QA_BRUTE : QA_TREE;
+    return a;
+}
+int ticket_query_count(edynhip_ctx *c, const QaTicket &t) {
+    const bool islands = (t.want_any & (EDYNHIP_WANT_ISLANDS | EDYNHIP_WANT_OF_INTEREST)) != 0;
+    EH_TRY(query_tree_prepare(c));
+    EH_TRY(qa_reserve(c, 4 * t.n, islands));
+    if (islands) { EH_TRY(prepare_islands(c)); }
+    const uint32_t n = t.n;
+    if (n == 0) return EDYNHIP_OK;
+    EH_HIP(c, hipMemsetAsync(t.cnt_k, 0, 3 * (size_t)n * sizeof(uint32_t), c->stream));   // (a category nobody wants is not counted)
+    EH_HIP(c, hipMemsetAsync(t.ctl, 0, 6 * sizeof(uint32_t), c->stream));
+    for (int k = 0; k < 3; ++k) {
+        if (!(t.want_any & (1u << k))) continue;
+        const QaArgs a = ticket_args(c, k, t.flags);
+        for (uint32_t off = 0; off < n; off += kQaChunk) {
+            const uint32_t m = std::min(kQaChunk, n - off);
+            hipLaunchKernelGGL(k_qa_count, dim3(nblocks(m, 256)), dim3(256), 0, c->stream, a, m, t.boxes_k + 2 * ((size_t)k * n + off), off, 1u,
+                               t.cnt_k + (size_t)k * n + off, t.mid + (size_t)k * n, t.big + (size_t)k * n, t.ctl + 2 * k);
+        }
+    }
+    EH_HIP(c, hipGetLastError());
+    return EDYNHIP_OK;
+}
+int ticket_query_scan(edynhip_ctx *c, const QaTicket &t) {
+    return scan_counts(c, *c->qa, 4 * t.n, t.cnt4, t.off4, t.tot, t.off4 + 4 * (size_t)t.n, nullptr);
+}
+int ticket_query_fill(edynhip_ctx *c, const QaTicket &t) {
+    const uint32_t n = t.n;
+    if (n == 0 || t.capacity == 0) return EDYNHIP_OK;
+    QueryAabb &q = *c->qa;
+    for (int k = 0; k < 3; ++k) {
+        if (!(t.want_any & (1u << k))) continue;
+        const QaArgs a = ticket_args(c, k, t.flags);
+        const float4 *boxes = t.boxes_k + 2 * (size_t)k * n;
+        const uint32_t *cnt = t.cnt_k + (size_t)k * n, *off = t.off_k + (size_t)k * n;
+        for (uint32_t o = 0; o < n; o += kQaChunk) {
+            const uint32_t m = std::min(kQaChunk, n - o);
+            hipLaunchKernelGGL(k_qa_fill, dim3(nblocks(m, 256)), dim3(256), 0, c->stream, a, m, boxes + 2 * (size_t)o, cnt + o, off + o, t.ids, t.capacity);
+        }
+        if (a.mode == QA_TREE) {
+            hipLaunchKernelGGL(k_qa_sort, dim3(std::min(n, 2048u)), dim3(64), 0, c->stream, t.mid + (size_t)k * n, t.ctl + 2 * k, cnt, off, t.ids, t.capacity, (unsigned long long *)(q.ctl + 4));
+            hipLaunchKernelGGL(k_qa_scan_fill, dim3(std::min(nblocks(n, 4), 1024u)), dim3(256), 0, c->stream, a, boxes, t.big + (size_t)k * n, t.ctl + 2 * k, off, t.ids, t.capacity, (unsigned long long *)(q.ctl + 4));
+        }
+    }
+    EH_HIP(c, hipGetLastError());
+    return EDYNHIP_OK;
+}
+IslandView ticket_island_view(edynhip_ctx *c) {
+    const QueryAabb &q = *c->qa;
+    return IslandView{c->query_island && c->step_index == 0 ? c->query_island : c->b.island, q.flag, q.slot, q.imin, q.imax};
 }
 
 }  // namespace eh

@@ -157,9 +157,14 @@ struct RayArgs {
 struct Best { dr::RayHit h; uint32_t body; };
 
 // One candidate: the ignore list, the candidate predicate, shape_raycast, and the keep-the-smallest rule (raycast.cpp:37-40; an exact
-// tie goes to the lower body index).
-DI void rc_candidate(const RayArgs &a, uint32_t body, f3 p0, f3 p1, Best &best) {
-    if (a.ignore && ((a.ignore[body >> 5] >> (body & 31u)) & 1u)) return;
+// tie goes to the lower body index). kList: the ignore list is the ray's own (lst[len], body indices in any order, duplicates and
+// indices beyond the body count allowed - the tickets of query_async.hip) instead of the call's bit mask.
+template <bool kList>
+DI void rc_candidate(const RayArgs &a, uint32_t body, f3 p0, f3 p1, Best &best, const uint32_t *lst, uint32_t len) {
+    if (kList) {
+        for (uint32_t k = 0; k < len; ++k)
+            if (lst[k] == body) return;
+    } else if (a.ignore && ((a.ignore[body >> 5] >> (body & 31u)) & 1u)) return;
     if (a.answers && !((a.answers[body >> 5] >> (body & 31u)) & 1u)) return;   // another shard's to answer
     const uint32_t fl = a.flags[body];
     const int st = (int)((fl & BF_SHAPE_MASK) >> BF_SHAPE_SHIFT);
@@ -180,22 +185,23 @@ DI void rc_candidate(const RayArgs &a, uint32_t body, f3 p0, f3 p1, Best &best) 
     if (h.fraction < best.h.fraction || (h.fraction == best.h.fraction && best.body != kNoBody && body < best.body)) { best.h = h; best.body = body; }
 }
 
-__global__ void __launch_bounds__(256) k_rc_trace(RayArgs a, uint32_t n, const float4 *__restrict__ P0, const float4 *__restrict__ P1, uint4 *__restrict__ out) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
+// One ray: the planes, then the tree along the ropes (or every body), and the record of the best hit.
+template <bool kList>
+DI void rc_trace(const RayArgs &a, uint32_t r, const float4 *__restrict__ P0, const float4 *__restrict__ P1, uint4 *__restrict__ out,
+                 const uint32_t *lst, uint32_t len) {
     const f3 p0 = from4(P0[r]), p1 = from4(P1[r]);
     Best best{dr::ray_miss(), kNoBody};
     if (a.brute) {
-        for (uint32_t b = 0; b < a.n_bodies; ++b) rc_candidate(a, b, p0, p1, best);
+        for (uint32_t b = 0; b < a.n_bodies; ++b) rc_candidate<kList>(a, b, p0, p1, best, lst, len);
     } else {
-        for (uint32_t k = 0; k < a.n_planes; ++k) rc_candidate(a, a.planes[k], p0, p1, best);
+        for (uint32_t k = 0; k < a.n_planes; ++k) rc_candidate<kList>(a, a.planes[k], p0, p1, best, lst, len);
         const float tol = kNodeGrow * (1.0f + max_abs(p0, p1));
         uint32_t node = a.n_tree ? 0u : kRayEnd;   // the root: internal node 0, or leaf 0 of a one-body tree
         while (node != kRayEnd) {
             const float4 lo = a.nmin[node], hi = a.nmax[node];
             const uint32_t w = __float_as_uint(lo.w);
             if (w & kLeafBit) {
-                rc_candidate(a, w & ~kLeafBit, p0, p1, best);   // the exact predicate on the body's own box
+                rc_candidate<kList>(a, w & ~kLeafBit, p0, p1, best, lst, len);   // the exact predicate on the body's own box
                 node = __float_as_uint(hi.w);
             } else if (dr::intersect_segment_aabb(p0, p1, mk3(lo.x - tol, lo.y - tol, lo.z - tol), mk3(hi.x + tol, hi.y + tol, hi.z + tol))) {
                 node = w;
@@ -207,6 +213,20 @@ __global__ void __launch_bounds__(256) k_rc_trace(RayArgs a, uint32_t n, const f
     const dr::RayHit &h = best.h;
     out[2 * (size_t)r] = make_uint4(best.body, __float_as_uint(h.fraction), __float_as_uint(h.normal.x), __float_as_uint(h.normal.y));
     out[2 * (size_t)r + 1] = make_uint4(__float_as_uint(h.normal.z), (uint32_t)h.feature, h.index, 0u);
+}
+
+__global__ void __launch_bounds__(256) k_rc_trace(RayArgs a, uint32_t n, const float4 *__restrict__ P0, const float4 *__restrict__ P1, uint4 *__restrict__ out) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    rc_trace<false>(a, r, P0, P1, out, nullptr, 0u);
+}
+// The tickets' rays: ray r ignores ign_ids[ign_off[r] .. ign_off[r + 1]) (a.ignore is not read). `out` may be pinned host memory.
+__global__ void __launch_bounds__(256) k_rc_trace_lists(RayArgs a, uint32_t n, const float4 *__restrict__ P0, const float4 *__restrict__ P1, uint4 *__restrict__ out,
+                                                        const uint32_t *__restrict__ ign_off, const uint32_t *__restrict__ ign_ids) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t lo = ign_off[r], hi = ign_off[r + 1];
+    rc_trace<true>(a, r, P0, P1, out, ign_ids + lo, hi - lo);
 }
 
 __global__ void k_rc_fill_u32(uint32_t *p, uint32_t n, uint32_t v) {
@@ -302,6 +322,22 @@ static int raycast_device(edynhip_ctx *c, uint32_t n, const void *p0_f4, const v
     uint4 *O = (uint4 *)out;
     for (uint32_t off = 0; off < n; off += kChunk)
         EH_TRY(launch(c, a, std::min(kChunk, n - off), P0 + off, P1 + off, O + 2 * (size_t)off));
+    return EDYNHIP_OK;
+}
+
+// A ticket's rays (query_async.hip): device arrays, ray r with the ignore list ign_ids[ign_off[r] .. ign_off[r + 1]) of its own
+// (ign_off == nullptr: no lists); enqueued on the context's stream. The call's bit mask (RayTree::mask) is neither written nor read.
+int ticket_trace(edynhip_ctx *c, uint32_t n, const float4 *p0, const float4 *p1, const uint32_t *ign_off, const uint32_t *ign_ids, uint32_t flags, uint4 *out) {
+    if (n == 0) return EDYNHIP_OK;
+    bool use_mask = false;
+    EH_TRY(prepare(c, 0, nullptr, use_mask));
+    const RayArgs a = ray_args(c, false, flags);
+    for (uint32_t off = 0; off < n; off += kChunk) {
+        const uint32_t m = std::min(kChunk, n - off);
+        if (!ign_off) { EH_TRY(launch(c, a, m, p0 + off, p1 + off, out + 2 * (size_t)off)); continue; }
+        hipLaunchKernelGGL(k_rc_trace_lists, dim3(nblocks(m, 256)), dim3(256), 0, c->stream, a, m, p0 + off, p1 + off, out + 2 * (size_t)off, ign_off + off, ign_ids);
+        EH_HIP(c, hipGetLastError());
+    }
     return EDYNHIP_OK;
 }
 

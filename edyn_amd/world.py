@@ -101,6 +101,7 @@ class World:
         self.num_meshes = 0
         self._mesh_sig = []   # content hashes of the meshes created through set_scene, in id order
         self._L = _capi.lib()
+        self._tickets = {}   # outstanding query tickets -> "rays" / "boxes" (query_collect picks the entry point by it)
 
     # ---- edyn::attach / detach
     def attach(self, max_bodies, max_joints=0):
@@ -135,6 +136,7 @@ class World:
         if self._h:
             self._L.edynhip_destroy(self._h)
             self._h = None
+            self._tickets = {}   # (the context took its tickets with it)
 
     def __del__(self):
         try:
@@ -495,6 +497,85 @@ class World:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._check(self._L.edynhip_query_aabb_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # ---- queries as tickets: edyn::raycast_async / query_aabb_async / query_aabb_of_interest_async (collision/raycast.hpp:170-182,
+    # collision/query_aabb.hpp:37-44). A submit enqueues the query behind everything enqueued so far and returns at once.
+    def raycast_submit(self, p0, p1, ignore=None, ignore_offsets=None, brute_force=False):
+        """Rays as in raycast(). ignore: one list of body indices per ray; or, with ignore_offsets[n + 1], the lists laid end to end -
+        ray i ignores ignore[ignore_offsets[i]:ignore_offsets[i + 1]]. Returns a ticket."""
+        a = np.ascontiguousarray(np.asarray(p0, np.float32).reshape(-1, 3))
+        b = np.ascontiguousarray(np.asarray(p1, np.float32).reshape(-1, 3))
+        if a.shape != b.shape:
+            raise ValueError("p0 and p1 must hold the same number of points")
+        off = ids = None
+        if ignore_offsets is not None:
+            off = np.ascontiguousarray(np.asarray(ignore_offsets, np.uint32).reshape(-1))
+            ids = np.ascontiguousarray(np.asarray(() if ignore is None else ignore, np.uint32).reshape(-1))
+            if len(off) != len(a) + 1:
+                raise ValueError("ignore_offsets must hold n + 1 entries")
+        elif ignore is not None:
+            lists = [np.asarray(l, np.uint32).reshape(-1) for l in ignore]
+            if len(lists) != len(a):
+                raise ValueError("ignore must hold one list per ray")
+            off = np.zeros(len(a) + 1, np.uint32)
+            off[1:] = np.cumsum([len(l) for l in lists])
+            ids = np.ascontiguousarray(np.concatenate(lists)) if lists else np.zeros(0, np.uint32)
+        t = C.c_uint64(0)
+        flags = _capi.RAYCAST_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_raycast_submit(self._h, len(a), _ptr(a), _ptr(b), _ptr(off) if off is not None else None,
+                                                   _ptr(ids) if ids is not None and len(ids) else None, flags, C.byref(t)))
+        self._tickets[t.value] = "rays"
+        return t.value
+
+    def query_aabb_submit(self, boxes, want, ids_capacity, brute_force=False):
+        """Boxes as in query_aabb(); want: _capi.WANT_* bits, one mask per box or one for all. Returns a ticket whose lists hold up to
+        ids_capacity ids together."""
+        b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 6))
+        w = np.asarray(want, np.uint8).reshape(-1)
+        if len(w) == 1 and len(b) != 1:
+            w = np.full(len(b), w[0], np.uint8)
+        w = np.ascontiguousarray(w)
+        if len(w) != len(b):
+            raise ValueError("want must hold one mask per box")
+        t = C.c_uint64(0)
+        flags = _capi.QUERY_BRUTE_FORCE if brute_force else 0
+        self._check(self._L.edynhip_query_aabb_submit(self._h, len(b), _ptr(b), _ptr(w) if len(w) else None, int(ids_capacity), flags, C.byref(t)))
+        self._tickets[t.value] = "boxes"
+        return t.value
+
+    def query_poll(self, ticket):
+        """True once the ticket's results are there. Never waits."""
+        done = C.c_int(0)
+        self._check(self._L.edynhip_query_poll(self._h, int(ticket), C.byref(done)))
+        return bool(done.value)
+
+    def query_collect(self, ticket):
+        """Waits for the ticket. Rays: a RAYCAST_HIT_DTYPE array as raycast() returns. Boxes: (offsets[4 n + 1], ids), list 4 i + k of box i
+        with k = 0 procedural, 1 non-procedural, 2 islands, 3 of interest. A box ticket whose lists do not fit its ids_capacity raises
+        EdynHipError (code -4) that carries .offsets and .total. The arrays are copies: they outlive query_release."""
+        kind = self._tickets.get(int(ticket))
+        if kind == "boxes":
+            v = _capi.QueryAabbView()
+            rc = self._L.edynhip_query_aabb_collect(self._h, int(ticket), C.byref(v))
+            if rc not in (0, -4):
+                self._check(rc)
+            offsets = np.ctypeslib.as_array(v.offsets, shape=(4 * v.n + 1,)).copy()
+            if rc != 0:
+                e = EdynHipError(rc, self._L.edynhip_last_error(self._h).decode())
+                e.offsets, e.total = offsets, int(v.total)
+                raise e
+            ids = np.ctypeslib.as_array(v.ids, shape=(int(v.total),)).copy() if v.total else np.zeros(0, np.uint32)
+            return offsets, ids
+        hits, n = C.c_void_p(None), C.c_uint32(0)   # (an unknown ticket: the library says so)
+        self._check(self._L.edynhip_raycast_collect(self._h, int(ticket), C.byref(hits), C.byref(n)))
+        out = np.zeros(n.value, _capi.RAYCAST_HIT_DTYPE)
+        if n.value:
+            C.memmove(_ptr(out), hits, out.nbytes)
+        return out
+
+    def query_release(self, ticket):
+        self._check(self._L.edynhip_query_release(self._h, int(ticket)))
+        self._tickets.pop(int(ticket), None)
 
     def get_manifolds(self):
         m = C.c_uint32(0)

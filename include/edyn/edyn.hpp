@@ -34,6 +34,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -41,6 +42,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <variant>
 #include <vector>
@@ -451,6 +453,7 @@ private:
     size_t count_{0};
 };
 
+struct async_queries;   // the requests of raycast_async / query_aabb_async / query_aabb_of_interest_async (defined with them, below)
 // The analogue of stepper_sequential in registry.ctx() (edyn.cpp:117-123).
 struct gpu_stepper {
     init_config cfg;
@@ -495,6 +498,7 @@ struct gpu_stepper {
     bool hooks_connected{false};
     bool host_presentation{false};                                  // this update's presentation transforms were not part of a write-back: compute them on the host
     uint32_t events_stale_through{0};                               // asynchronous mode: snapshots up to this step index carry events a rebuild already covered
+    std::shared_ptr<async_queries> queries;                         // asynchronous mode: queued and in-flight query requests (nullptr until the first request)
     ~gpu_stepper() { if (ctx) edynhip_destroy(ctx); if (world) edynhip_world_destroy(world); }
 };
 struct body_index { uint32_t value; };
@@ -1305,7 +1309,25 @@ inline void import_pending_records(entt::registry &registry, gpu_stepper &s, con
     } else if (view.num_events) ev.assign(view.events, view.events + view.num_events);
     apply_contact_events(registry, s, ev, EDYNHIP_OK);
 }
+// Queries in asynchronous mode (raycast_async, query_aabb_async, query_aabb_of_interest_async; defined with them, below): an update
+// flushes the queued requests as one raycast ticket and one AABB ticket - after sync_removed and before this update's uploads and steps
+// (on the very first update, or when this update's scene upload re-creates the context and with it every ticket: right after the
+// upload, still before the steps) - and delivers the answers at its end, when the registry has received what this update delivers.
+// An update that throws gives its tickets back and keeps the requests for the next one (abandon_queries).
+inline void flush_queries(entt::registry &registry, gpu_stepper &s);
+inline void deliver_queries(entt::registry &registry, gpu_stepper &s);
+inline void abandon_queries(gpu_stepper &s);
+inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsigned steps, bool timed, double first_time, double step_dt);
 inline void run_steps(entt::registry &registry, gpu_stepper &s, unsigned steps, bool timed = false, double first_time = 0, double step_dt = 0) {
+    try {
+        run_steps_of_update(registry, s, steps, timed, first_time, step_dt);
+        if (s.queries) deliver_queries(registry, s);
+    } catch (...) {
+        if (s.queries) abandon_queries(s);
+        throw;
+    }
+}
+inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsigned steps, bool timed, double first_time, double step_dt) {
     const bool async = s.cfg.execution_mode == execution_mode::asynchronous;
     if (async && s.records_pending && (s.state_dirty || s.scene_dirty || steps == 0 || s.pre_step || s.post_step)) {
         // execution_mode::asynchronous, the cases that cannot overlap: user edits pending (the snapshot is superseded by the device's
@@ -1352,12 +1374,17 @@ inline void run_steps(entt::registry &registry, gpu_stepper &s, unsigned steps, 
         return;
     }
     { phase_timer t(s.tm.sync_removed); sync_removed(registry, s); }
+    {   // before the uploads - edits made since the last update are not seen - unless upload_scene is about to re-create the context
+        const bool recreates = s.scene_dirty && (s.bodies.size() > s.capacity || s.constraints.size() > s.joint_capacity || s.recreate);
+        if (s.queries && s.ctx && !recreates) flush_queries(registry, s);
+    }
     {
         phase_timer t(s.tm.upload);
         if (s.scene_dirty) upload_scene(registry, s);
         if (s.state_dirty) upload_state(registry, s);   // also after an append: edits made in the same frame are not lost
         apply_params(s);
     }
+    if (s.queries) flush_queries(registry, s);   // (nothing left to flush when it ran above)
     if (steps == 0 || s.bodies.empty()) { s.host_presentation = true; return; }   // time went on without a step: presentation from the registry's state
     s.tm.steps += steps;
     if (s.pre_step || s.post_step) {
@@ -1710,15 +1737,224 @@ template <typename Func>
 inline void query_non_procedural_aabb(entt::registry &registry, const std::vector<AABB> &aabbs, Func func) {
     detail::query_aabb_batch(registry, EDYNHIP_QUERY_NON_PROCEDURAL, aabbs.data(), aabbs.size(), func, "edyn::query_non_procedural_aabb");
 }
-/// collision/query_aabb.hpp:37-44: the asynchronous queries belong to execution_mode::asynchronous's worker, which this stepper does not
-/// have; they are declared for source compatibility and throw stepper_error in every mode.
-template <typename Delegate>
-inline query_aabb_id_type query_aabb_async(entt::registry &, const AABB &, const Delegate &, bool, bool, bool) {
-    throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::query_aabb_async: not provided (use query_procedural_aabb / query_non_procedural_aabb in a sequential mode)");
+// ---- collision/raycast.hpp:153-182, collision/query_aabb.hpp:34-44: the queries of execution_mode::asynchronous. The reference sends
+// each request to its simulation worker, which answers from its own registry between steps (simulation_worker.cpp:600-692) and sends
+// the answer back; the delegate fires in a later edyn::update. Here the requests queue on the host; the next edyn::update flushes them
+// as one raycast ticket and one AABB ticket (edynhip_raycast_submit / edynhip_query_aabb_submit) before its own uploads and steps -
+// so they are answered from the state the previous update left on the device, edits made since not included, as the worker's registry
+// would not have them either - and calls the delegates at its end, in request order, rays first, when the registry has received what
+// that update delivers: on the overlapping path exactly the state the answers were computed from. An update that runs no step still
+// answers. A request made inside a delegate goes to the next update; edyn::detach drops what is pending without calling anybody.
+#ifndef EDYN_QUERY_IDS_CAPACITY
+#define EDYN_QUERY_IDS_CAPACITY 4096   // ids the AABB ticket of one update holds at first; an update whose lists need more asks again with the total
+#endif
+using raycast_id_type = unsigned;
+static constexpr auto invalid_raycast_id = std::numeric_limits<raycast_id_type>::max();
+#if __has_include(<entt/entt.hpp>)
+using raycast_delegate_type = entt::delegate<void(raycast_id_type, const raycast_result &, vector3, vector3)>;
+#endif
+namespace detail {
+struct async_queries {
+    struct ray_request {
+        raycast_id_type id; vector3 p0, p1; std::vector<entt::entity> ignore;
+        std::function<void(raycast_id_type, const raycast_result &, vector3, vector3)> fn;
+    };
+    struct box_request {
+        query_aabb_id_type id; AABB box; uint8_t want; bool of_interest;
+        std::function<void(query_aabb_id_type, const query_aabb_result &)> fn;
+    };
+    struct box_batch { std::vector<box_request> requests; uint64_t ticket{0}; uint32_t capacity{0}; };   // one AABB ticket
+    std::vector<ray_request> rays, rays_flight;     // queued since the last flush; submitted with ray_ticket
+    std::vector<box_request> boxes;                 // queued since the last flush
+    // in flight: [0] the requests whose lists did not fit last time, asked again with the reported total - a ticket of their own, so
+    // that newer requests cannot make them overflow again; [1] the requests queued since the last flush
+    box_batch flight[2];
+    std::vector<box_request> again; uint32_t again_capacity{0};   // what [0] takes up at the next flush
+    uint64_t ray_ticket{0};                         // 0: none (nothing in flight, or no context to ask)
+    bool flushed{false};                            // this update has flushed
+    raycast_id_type next_ray{0};
+    query_aabb_id_type next_box{0};
+    uint32_t ids_capacity{EDYN_QUERY_IDS_CAPACITY};
+};
+inline async_queries &queries_of(gpu_stepper &s, const char *who) {
+    if (s.cfg.execution_mode != execution_mode::asynchronous)
+        throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": only in execution_mode::asynchronous (a sequential mode answers edyn::raycast / query_procedural_aabb / query_non_procedural_aabb at once)").c_str());
+    if (s.multi()) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": a world over several devices (init_config::devices) has no queries").c_str());
+    if (!s.queries) s.queries = std::make_shared<async_queries>();
+    return *s.queries;
 }
+inline void flush_queries(entt::registry &registry, gpu_stepper &s) {
+    async_queries &q = *s.queries;
+    if (q.flushed) return;
+    q.flushed = true;
+    q.rays_flight.swap(q.rays);
+    q.flight[0].requests.swap(q.again); q.flight[0].capacity = q.again_capacity;
+    q.flight[1].requests.swap(q.boxes); q.flight[1].capacity = q.ids_capacity;
+    q.ray_ticket = q.flight[0].ticket = q.flight[1].ticket = 0;
+    if (!s.ctx || s.bodies.empty()) return;   // nothing to ask: every answer is empty
+    if (!q.rays_flight.empty()) {
+        const size_t n = q.rays_flight.size();
+        std::vector<float> a(3 * n), b(3 * n);
+        std::vector<uint32_t> off(n + 1, 0u), ids;
+        for (size_t i = 0; i < n; ++i) {
+            const auto &r = q.rays_flight[i];
+            a[3 * i] = r.p0.x; a[3 * i + 1] = r.p0.y; a[3 * i + 2] = r.p0.z;
+            b[3 * i] = r.p1.x; b[3 * i + 1] = r.p1.y; b[3 * i + 2] = r.p1.z;
+            const std::vector<uint32_t> ign = raycast_ignore(registry, r.ignore);   // entities -> body indices now: destroyed ones drop out
+            ids.insert(ids.end(), ign.begin(), ign.end());
+            off[i + 1] = (uint32_t)ids.size();
+        }
+        check(s, edynhip_raycast_submit(s.ctx, (uint32_t)n, a.data(), b.data(), off.data(), ids.empty() ? nullptr : ids.data(), 0, &q.ray_ticket));
+    }
+    for (async_queries::box_batch &batch : q.flight) {
+        const size_t n = batch.requests.size();
+        if (n == 0) continue;
+        std::vector<float> b(6 * n);
+        std::vector<uint8_t> want(n);
+        for (size_t i = 0; i < n; ++i) {
+            const AABB &x = batch.requests[i].box;
+            b[6 * i] = x.min.x; b[6 * i + 1] = x.min.y; b[6 * i + 2] = x.min.z;
+            b[6 * i + 3] = x.max.x; b[6 * i + 4] = x.max.y; b[6 * i + 5] = x.max.z;
+            want[i] = batch.requests[i].want;
+        }
+        check(s, edynhip_query_aabb_submit(s.ctx, (uint32_t)n, b.data(), want.data(), batch.capacity, 0, &batch.ticket));
+    }
+}
+// the lists of one AABB ticket as entities; false: they did not fit the ticket (*total: what they need)
+inline bool collect_boxes(entt::registry &registry, gpu_stepper &s, async_queries::box_batch &batch, std::vector<query_aabb_result> &lists, uint64_t *total) {
+    lists.assign(batch.requests.size(), query_aabb_result{});
+    if (!batch.ticket) return true;
+    edynhip_query_aabb_view v{};
+    const int rc = edynhip_query_aabb_collect(s.ctx, batch.ticket, &v);
+    if (rc == EDYNHIP_OK) {
+        auto entities = [&](size_t list, std::vector<entt::entity> &out) {
+            for (uint32_t k = v.offsets[list]; k < v.offsets[list + 1]; ++k)
+                if (v.ids[k] < s.bodies.size() && s.bodies[v.ids[k]] != entt::null) out.push_back(s.bodies[v.ids[k]]);
+        };
+        for (size_t i = 0; i < batch.requests.size() && i < v.n; ++i) {
+            query_aabb_result &r = lists[i];
+            entities(4 * i + 1, r.non_procedural_entities);
+            if (!batch.requests[i].of_interest) { entities(4 * i, r.procedural_entities); continue; }
+            // of interest (simulation_worker.cpp:641-692): the bodies of the islands the box meets, then the constraints that hold one
+            // of them, in creation order (the worker's island.edges without the contact manifolds)
+            entities(4 * i + 3, r.procedural_entities);
+            const std::vector<uint32_t> members(v.ids + v.offsets[4 * i + 3], v.ids + v.offsets[4 * i + 4]);   // ascending
+            const size_t first_constraint = r.procedural_entities.size();
+            for (size_t j = 0; j < s.constraints.size(); ++j) {
+                const entt::entity e = s.constraints[j];
+                if (e == entt::null) continue;
+                const constraint_base *cb = constraint_of(registry, e, s.constraint_kind[j]);
+                if (!cb) continue;
+                bool holds = false;
+                for (int k = 0; k < 2; ++k)
+                    if (registry.valid(cb->body[k]))
+                        if (auto *bi = registry.try_get<body_index>(cb->body[k])) holds = holds || std::binary_search(members.begin(), members.end(), bi->value);
+                if (holds && std::find(r.procedural_entities.begin() + (std::ptrdiff_t)first_constraint, r.procedural_entities.end(), e) == r.procedural_entities.end())
+                    r.procedural_entities.push_back(e);   // (an entity that carries two constraint types is listed once)
+            }
+        }
+    }
+    (void)edynhip_query_release(s.ctx, batch.ticket);
+    batch.ticket = 0;
+    *total = v.total;
+    if (rc == EDYNHIP_ERR_CAPACITY) return false;
+    check(s, rc);
+    return true;
+}
+// The update threw: the tickets in flight go back, their requests wait in front of the newer ones for the next update's flush.
+inline void abandon_queries(gpu_stepper &s) {
+    async_queries &q = *s.queries;
+    q.flushed = false;
+    if (s.ctx) {
+        if (q.ray_ticket) (void)edynhip_query_release(s.ctx, q.ray_ticket);
+        for (async_queries::box_batch &batch : q.flight) if (batch.ticket) (void)edynhip_query_release(s.ctx, batch.ticket);
+    }
+    q.ray_ticket = q.flight[0].ticket = q.flight[1].ticket = 0;
+    auto put_back = [](auto &flight, auto &pending) {
+        pending.insert(pending.begin(), std::make_move_iterator(flight.begin()), std::make_move_iterator(flight.end()));
+        flight.clear();
+    };
+    put_back(q.rays_flight, q.rays);
+    if (!q.flight[0].requests.empty()) q.again_capacity = std::max(q.again_capacity, q.flight[0].capacity);
+    put_back(q.flight[0].requests, q.again);
+    put_back(q.flight[1].requests, q.boxes);
+}
+inline void deliver_queries(entt::registry &registry, gpu_stepper &s) {
+    async_queries &q = *s.queries;
+    if (!q.flushed) flush_queries(registry, s);   // (an update that took a path without uploads)
+    q.flushed = false;
+    // the answers first, then the delegates: a delegate may make requests (they go to the next update) or destroy entities
+    std::vector<async_queries::ray_request> rays; rays.swap(q.rays_flight);
+    std::vector<raycast_result> hits(rays.size());
+    if (q.ray_ticket) {
+        const edynhip_raycast_hit *h = nullptr; uint32_t n = 0;
+        const int rc = edynhip_raycast_collect(s.ctx, q.ray_ticket, &h, &n);
+        if (rc == EDYNHIP_OK) for (uint32_t i = 0; i < n && i < hits.size(); ++i) hits[i] = to_raycast_result(s, h[i]);
+        (void)edynhip_query_release(s.ctx, q.ray_ticket);
+        q.ray_ticket = 0;
+        check(s, rc);
+    }
+    std::vector<async_queries::box_request> boxes[2];
+    std::vector<query_aabb_result> lists[2];
+    q.again_capacity = 0;   // (q.again went into flight[0] at the flush)
+    for (int k = 0; k < 2; ++k) {
+        uint64_t total = 0;
+        const bool fit = collect_boxes(registry, s, q.flight[k], lists[k], &total);
+        boxes[k].swap(q.flight[k].requests);
+        if (fit) continue;
+        // these lists need more ids than their ticket held: the same requests go up again with the next flush - which sees the state
+        // this update's steps leave, as their delegates will - with room for the reported total; later tickets start with that room too
+        const uint32_t need = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFEull);
+        q.again.insert(q.again.end(), std::make_move_iterator(boxes[k].begin()), std::make_move_iterator(boxes[k].end()));
+        q.again_capacity = (uint32_t)std::min<uint64_t>((uint64_t)q.again_capacity + need, 0xFFFFFFFEull);   // (both tickets of one update may ask again)
+        q.ids_capacity = std::max(q.ids_capacity, need);
+        boxes[k].clear();
+    }
+    for (size_t i = 0; i < rays.size(); ++i) rays[i].fn(rays[i].id, hits[i], rays[i].p0, rays[i].p1);
+    for (int k = 0; k < 2; ++k)
+        for (size_t i = 0; i < boxes[k].size(); ++i) boxes[k][i].fn(boxes[k][i].id, lists[k][i]);
+}
+}  // namespace detail
+/// edyn::raycast_async (collision/raycast.hpp:170-182): the ray is answered by the next edyn::update, which calls
+/// delegate(id, result, p0, p1). delegate: any callable with that signature (raycast_delegate_type where the registry library has
+/// delegates). ignore_entities become body indices when the update flushes; entities destroyed by then drop out. Ids ascend.
 template <typename Delegate>
-inline query_aabb_id_type query_aabb_of_interest_async(entt::registry &, const AABB &, const Delegate &) {
-    throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::query_aabb_of_interest_async: not provided (use query_procedural_aabb / query_non_procedural_aabb in a sequential mode)");
+inline raycast_id_type raycast_async(entt::registry &registry, vector3 p0, vector3 p1, const Delegate &delegate,
+                                     const std::vector<entt::entity> &ignore_entities = {}) {
+    auto &q = detail::queries_of(registry.ctx().get<detail::gpu_stepper>(), "edyn::raycast_async");
+    if constexpr (std::is_invocable_v<const Delegate &, raycast_id_type, const raycast_result &, vector3, vector3>) {
+        q.rays.push_back({q.next_ray, p0, p1, ignore_entities, [delegate](raycast_id_type id, const raycast_result &r, vector3 a, vector3 b) { delegate(id, r, a, b); }});
+        return q.next_ray++;
+    } else throw stepper_error(EDYNHIP_ERR_INVALID, "edyn::raycast_async: the delegate cannot be called with (raycast_id_type, const raycast_result &, vector3, vector3)");
+}
+namespace detail {
+template <typename Delegate>
+inline query_aabb_id_type queue_box(entt::registry &registry, const AABB &aabb, const Delegate &delegate, uint8_t want, bool of_interest, const char *who) {
+    auto &q = queries_of(registry.ctx().get<gpu_stepper>(), who);
+    if constexpr (std::is_invocable_v<const Delegate &, query_aabb_id_type, const query_aabb_result &>) {
+        q.boxes.push_back({q.next_box, aabb, want, of_interest, [delegate](query_aabb_id_type id, const query_aabb_result &r) { delegate(id, r); }});
+        return q.next_box++;
+    } else throw stepper_error(EDYNHIP_ERR_INVALID, (std::string(who) + ": the delegate cannot be called with (query_aabb_id_type, const query_aabb_result &)").c_str());
+}
+}  // namespace detail
+/// edyn::query_aabb_async (collision/query_aabb.hpp:37-41): the box is answered by the next edyn::update, which calls
+/// delegate(id, result) with the lists that were asked for. result.island_entities stays empty: this stepper has no island entities
+/// (islands are labels on the device; edynhip_query_aabb_submit with EDYNHIP_WANT_ISLANDS reports them), so query_islands = true
+/// throws stepper_error at the call.
+template <typename Delegate>
+inline query_aabb_id_type query_aabb_async(entt::registry &registry, const AABB &aabb, const Delegate &delegate, bool query_procedural,
+                                           bool query_non_procedural, bool query_islands) {
+    (void)detail::queries_of(registry.ctx().get<detail::gpu_stepper>(), "edyn::query_aabb_async");   // (the mode first: a sequential mode refuses whatever is asked)
+    if (query_islands) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn::query_aabb_async: query_islands - this stepper has no island entities");
+    const uint8_t want = (uint8_t)((query_procedural ? EDYNHIP_WANT_PROCEDURAL : 0) | (query_non_procedural ? EDYNHIP_WANT_NON_PROCEDURAL : 0));
+    return detail::queue_box(registry, aabb, delegate, want, false, "edyn::query_aabb_async");
+}
+/// edyn::query_aabb_of_interest_async (collision/query_aabb.hpp:43-44, simulation_worker.cpp:641-692): procedural_entities = the dynamic
+/// bodies of every island whose box meets the AABB, in creation order, then the constraint entities that hold one of them, in creation
+/// order; non_procedural_entities = the static and kinematic bodies in the AABB. island_entities stays empty (no island entities here).
+template <typename Delegate>
+inline query_aabb_id_type query_aabb_of_interest_async(entt::registry &registry, const AABB &aabb, const Delegate &delegate) {
+    return detail::queue_box(registry, aabb, delegate, (uint8_t)(EDYNHIP_WANT_OF_INTEREST | EDYNHIP_WANT_NON_PROCEDURAL), true, "edyn::query_aabb_of_interest_async");
 }
 
 // ---- util/rigidbody.hpp:84-93, rigidbody.cpp:47-191

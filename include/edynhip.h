@@ -350,6 +350,52 @@ int edynhip_query_aabb_device(edynhip_ctx *ctx, int category, uint32_t n, const 
  * scripts/bench_query_aabb.py --ratios and for tests that steer queries onto one path. */
 int edynhip_query_aabb_stats(edynhip_ctx *ctx, uint64_t *wave_sorted, uint64_t *wave_filled);
 
+/* Queries as TICKETS (additive to ABI 15): what edyn::raycast_async (include/edyn/collision/raycast.hpp:170-182), edyn::query_aabb_async
+ * and edyn::query_aabb_of_interest_async (include/edyn/collision/query_aabb.hpp:37-44) need - the reference's worker answers them between
+ * steps (src/edyn/simulation/simulation_worker.cpp:600-692) and the caller picks the answer up later. A submit enqueues the query on the
+ * context's stream and returns a ticket without waiting for the device: the ticket answers from the state after everything enqueued on
+ * the context before the submit (steps, edynhip_set_state, edits) and nothing enqueued after it. The inputs are copied before submit
+ * returns. edynhip_query_poll never waits; a collect waits until the ticket is done. Results live in pinned memory the context owns,
+ * valid until edynhip_query_release (or edynhip_destroy, which frees outstanding tickets). At most EDYNHIP_QUERY_TICKETS_MAX tickets are
+ * outstanding: one more submit returns EDYNHIP_ERR_CAPACITY and disturbs none of them. Ticket values are never reused; a released or
+ * unknown ticket, or one of the other kind, is EDYNHIP_ERR_INVALID. Tickets may be collected in any order, more than once, and share no
+ * buffer with the synchronous entry points, which may be called between submit and collect. A shard context of a multi-device world:
+ * EDYNHIP_ERR_UNSUPPORTED. */
+enum { EDYNHIP_QUERY_TICKETS_MAX = 8 };
+enum { EDYNHIP_WANT_PROCEDURAL = 1, EDYNHIP_WANT_NON_PROCEDURAL = 2, EDYNHIP_WANT_ISLANDS = 4, EDYNHIP_WANT_OF_INTEREST = 8 };
+/* edyn::raycast_async (raycast.hpp:170-182; the worker: simulation_worker.cpp:600-624): n rays p0[n][3] -> p1[n][3], each with an ignore
+ * list of its own: ray i ignores ignore_ids[ignore_offsets[i] .. ignore_offsets[i + 1]) (NULL offsets: no list). Ray i gets the record
+ * edynhip_raycast(ctx, 1, p0_i, p1_i, its list, flags) would return: indices beyond the body count are skipped, duplicates are allowed.
+ * flags as edynhip_raycast. Offsets that descend, or unknown flag bits: EDYNHIP_ERR_INVALID. */
+int edynhip_raycast_submit(edynhip_ctx *ctx, uint32_t n, const float *p0, const float *p1,
+                           const uint32_t *ignore_offsets, const uint32_t *ignore_ids, uint32_t flags, uint64_t *ticket);
+/* edyn::query_aabb_async / query_aabb_of_interest_async (query_aabb.hpp:37-44; the worker: simulation_worker.cpp:626-692): n boxes
+ * boxes6[n][6] = (min, max), want[n] = EDYNHIP_WANT_* bits per box. Box i has four lists, 4 i + k: k = 0 procedural, 1 non-procedural,
+ * 2 islands - each what edynhip_query_aabb returns for the box in that category - and 3 "of interest": every dynamic body that has a
+ * shape and is not removed whose island (the label edynhip_get_derived returns) is one the islands category reports for the box, in
+ * ascending body index (the entities the worker collects from the islands it finds, simulation_worker.cpp:652-660). A list that was
+ * not wanted is empty. ids_capacity: the ids the ticket may hold. flags as edynhip_query_aabb. Unknown want or flag bits:
+ * EDYNHIP_ERR_INVALID. */
+int edynhip_query_aabb_submit(edynhip_ctx *ctx, uint32_t n, const float *boxes6, const uint8_t *want,
+                              uint32_t ids_capacity, uint32_t flags, uint64_t *ticket);
+/* *done = 1 once the ticket's results are in place (the worker's reply has arrived, simulation_worker.cpp:600-692). Never waits. */
+int edynhip_query_poll(edynhip_ctx *ctx, uint64_t ticket, int *done);
+/* The records of a raycast ticket (raycast.hpp:170-182: what the delegate receives), (*hits)[*n]; waits until they are there. */
+int edynhip_raycast_collect(edynhip_ctx *ctx, uint64_t ticket, const edynhip_raycast_hit **hits, uint32_t *n);
+typedef struct {
+    uint32_t n;               /* boxes of the ticket */
+    const uint32_t *offsets;  /* [4 n + 1]: list 4 i + k is ids[offsets[4 i + k] .. offsets[4 i + k + 1]); saturated at 0xFFFFFFFF */
+    const uint32_t *ids;      /* NULL when total > the ticket's ids_capacity */
+    uint64_t total;           /* ids of all lists together */
+} edynhip_query_aabb_view;
+/* The lists of a box ticket (query_aabb.hpp:37-44: what the delegate receives); waits until they are there. total > ids_capacity:
+ * returns EDYNHIP_ERR_CAPACITY with offsets and total valid and ids = NULL (submit again with ids_capacity = total): no list is ever
+ * cut short. */
+int edynhip_query_aabb_collect(edynhip_ctx *ctx, uint64_t ticket, edynhip_query_aabb_view *view);
+/* Gives the ticket's slot back (done or not: the slot's buffers are reused only by work enqueued later on the same stream); the
+ * pointers a collect returned for it are no longer valid (simulation_worker.cpp:600-692: the request is answered once). */
+int edynhip_query_release(edynhip_ctx *ctx, uint64_t ticket);
+
 /* Manifolds are kept (and returned) in ascending canonical order: key = (owner << 32) | other, where the owner is the
  * pair's procedural (dynamic) body - the one with the higher index when both are dynamic. edynhip_set_manifolds expects
  * records in that order. (EnTT's pool order is not reproducible; the solver visits manifolds in this order.) */
