@@ -54,7 +54,7 @@ class Stats(C.Structure):
 
 
 class WorldStats(C.Structure):   # edynhip_world_stats
-    _fields_ = [(n, C.c_uint32) for n in ("num_shards", "num_bodies", "steps", "approach_checks", "repartitions")] + [("bodies_per_shard", C.c_uint32 * 16), ("rebalances", C.c_uint32)]
+    _fields_ = [(n, C.c_uint32) for n in ("num_shards", "num_bodies", "steps", "approach_checks", "repartitions")] + [("bodies_per_shard", C.c_uint32 * 16), ("rebalances", C.c_uint32), ("extras_carries", C.c_uint32)]
 
 
 class WorldEditStats(C.Structure):   # edynhip_world_edit_stats
@@ -151,7 +151,10 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_world_edit_joint", "edynhip_world_edit_exclusion", "edynhip_world_set_state", "edynhip_world_get_params",
            "edynhip_world_set_params", "edynhip_world_get_edit_stats", "edynhip_world_get_asleep",
            # record hand-over of a multi-device world
-           "edynhip_world_snapshot_records", "edynhip_world_snapshot_map"]
+           "edynhip_world_snapshot_records", "edynhip_world_snapshot_map",
+           # materials and the mix table on a multi-device world
+           "edynhip_world_set_material_extras", "edynhip_world_set_material_ids", "edynhip_world_insert_material_mixing",
+           "edynhip_world_get_point_extras"]
 
 _lib = None
 
@@ -281,6 +284,10 @@ def lib():
         L.edynhip_world_get_asleep.argtypes = [C.c_void_p, C.c_void_p]
         L.edynhip_world_snapshot_records.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32]
         L.edynhip_world_snapshot_map.argtypes = [C.c_void_p, C.POINTER(RecordView)]
+        L.edynhip_world_set_material_extras.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.edynhip_world_set_material_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.edynhip_world_insert_material_mixing.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.edynhip_world_get_point_extras.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_partition_islands.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_island_boxes_overlap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_get_island_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]

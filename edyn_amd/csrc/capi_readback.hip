@@ -264,6 +264,7 @@ int edynhip_set_manifolds(edynhip_ctx *c, const edynhip_manifold *in, uint32_t n
 
 int edynhip_get_point_extras(edynhip_ctx *c, float *out7, uint32_t capacity, uint32_t *n) {
     if (!c || !n) return EDYNHIP_ERR_INVALID;
+    if (c->world_shard) return set_error(c, EDYNHIP_ERR_UNSUPPORTED, "edynhip_get_point_extras: a shard of a multi-device world is read through edynhip_world_get_point_extras");
     const uint32_t M = c->num_manifolds;
     *n = M;
     if (M == 0 || !out7) return EDYNHIP_OK;

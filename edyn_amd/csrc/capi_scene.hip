@@ -890,9 +890,9 @@ static int rebuild_mix_table(edynhip_ctx *c) {
 }
 }  // namespace eh
 
-extern "C" {
+namespace eh {
 
-int edynhip_set_material_extras(edynhip_ctx *c, uint32_t first, uint32_t n, const float *spin, const float *roll, const float *stiffness, const float *damping) {
+int shard_set_material_extras(edynhip_ctx *c, uint32_t first, uint32_t n, const float *spin, const float *roll, const float *stiffness, const float *damping) {
     if (!c) return EDYNHIP_ERR_INVALID;
     if ((uint64_t)first + n > c->b.n) return set_error(c, EDYNHIP_ERR_INVALID, "edynhip_set_material_extras: body range out of bounds");
     if (n == 0) return EDYNHIP_OK;
@@ -909,7 +909,7 @@ int edynhip_set_material_extras(edynhip_ctx *c, uint32_t first, uint32_t n, cons
     EH_HIP(c, hipStreamSynchronize(c->stream));
     return EDYNHIP_OK;
 }
-int edynhip_set_material_ids(edynhip_ctx *c, uint32_t first, uint32_t n, const uint32_t *ids) {
+int shard_set_material_ids(edynhip_ctx *c, uint32_t first, uint32_t n, const uint32_t *ids) {
     if (!c || (n && !ids)) return EDYNHIP_ERR_INVALID;
     if ((uint64_t)first + n > c->b.n) return set_error(c, EDYNHIP_ERR_INVALID, "edynhip_set_material_ids: body range out of bounds");
     for (uint32_t i = 0; i < n; ++i) if (ids[i] > 0xFFFFu) return set_error(c, EDYNHIP_ERR_INVALID, "edynhip_set_material_ids: material::id_type is 16 bits (0xFFFF = unassigned)");
@@ -918,12 +918,46 @@ int edynhip_set_material_ids(edynhip_ctx *c, uint32_t first, uint32_t n, const u
     for (uint32_t i = 0; i < n; ++i) c->mix.mat_id[first + i] = ids[i];
     return rebuild_mix_table(c);
 }
-int edynhip_insert_material_mixing(edynhip_ctx *c, uint32_t id0, uint32_t id1, const float *material6) {
+int shard_insert_material_mixing(edynhip_ctx *c, uint32_t id0, uint32_t id1, const float *material6) {
     if (!c || !material6) return EDYNHIP_ERR_INVALID;
     if (id0 >= 0xFFFFu || id1 >= 0xFFFFu) return set_error(c, EDYNHIP_ERR_INVALID, "edynhip_insert_material_mixing: unassigned material id");
     EH_HIP(c, hipSetDevice(c->device));
     c->mix.host[MixIdPair{id0, id1}] = {material6[0], material6[1], material6[2], material6[3], material6[4], material6[5]};
     return rebuild_mix_table(c);
+}
+// An empty mix table, before the bodies of a (re)built shard go up: the world replays its insertions, in their order, afterwards. The table is the reference's
+// std::map under unordered_pair's comparator, which is no strict weak order - inserting (1, 0) into a table that holds only (0, 1)
+// overwrites that entry, into one that also holds (0, 2) and (1, 2) it makes a new one - so a replay on top of what a kept context
+// still holds would build another table than the one context that took the same insertions once.
+int shard_reset_material_mixing(edynhip_ctx *c) {
+    c->mix.host.clear();
+    c->b.mix_K = 0;
+    return EDYNHIP_OK;
+}
+int shard_ensure_extras_storage(edynhip_ctx *c) {
+    EH_HIP(c, hipSetDevice(c->device));
+    return ensure_extras_storage(c);
+}
+
+}  // namespace eh
+
+extern "C" {
+
+// (a shard of a multi-device world holds part of the world's bodies in local indices: its materials are the world's, edynhip_world_set_material_extras ...)
+static int refuse_shard(edynhip_ctx *c, const char *who) {
+    return set_error(c, EDYNHIP_ERR_UNSUPPORTED, (std::string(who) + ": a shard of a multi-device world takes its materials from the world").c_str());
+}
+int edynhip_set_material_extras(edynhip_ctx *c, uint32_t first, uint32_t n, const float *spin, const float *roll, const float *stiffness, const float *damping) {
+    if (c && c->world_shard) return refuse_shard(c, "edynhip_set_material_extras");
+    return shard_set_material_extras(c, first, n, spin, roll, stiffness, damping);
+}
+int edynhip_set_material_ids(edynhip_ctx *c, uint32_t first, uint32_t n, const uint32_t *ids) {
+    if (c && c->world_shard) return refuse_shard(c, "edynhip_set_material_ids");
+    return shard_set_material_ids(c, first, n, ids);
+}
+int edynhip_insert_material_mixing(edynhip_ctx *c, uint32_t id0, uint32_t id1, const float *material6) {
+    if (c && c->world_shard) return refuse_shard(c, "edynhip_insert_material_mixing");
+    return shard_insert_material_mixing(c, id0, id1, material6);
 }
 
 }  // extern "C"

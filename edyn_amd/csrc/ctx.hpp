@@ -622,6 +622,20 @@ constexpr uint32_t kEventTagShift = 28, kEventTagShards = 16;   // id low word: 
 int shard_translate_events(edynhip_ctx *c, uint32_t expected, const uint32_t *local_ids_dev, uint32_t n_local, void *out);
 int shard_gather_point_ids(edynhip_ctx *c, uint64_t *ids_dev);
 int shard_inject_point_ids(edynhip_ctx *c, const uint64_t *ids_dev, uint32_t num_manifolds);
+// world_extras.hip: the current manifold array's point extras (Manifolds::xmat / ximp) as rows[num_manifolds][4][2] float4 on the device
+// (world_rules.hpp: the row layout), and the same table written back over what edynhip_set_manifolds mixed afresh. Both do nothing on a
+// context that keeps no extras storage.
+int shard_gather_point_extras(edynhip_ctx *c, void *rows_dev);
+int shard_inject_point_extras(edynhip_ctx *c, const void *rows_dev, uint32_t num_manifolds);
+bool shard_has_extras_storage(const edynhip_ctx *c);
+// capi_scene.hip: edynhip_set_material_extras / _set_material_ids / _insert_material_mixing as the world applies them to a shard (the
+// public calls refuse one: its bodies are the world's, in local indices), the empty mix table a (re)built shard replays the world's
+// insertions into, and the extras storage a carried point may need by itself
+int shard_set_material_extras(edynhip_ctx *c, uint32_t first, uint32_t n, const float *spin, const float *roll, const float *stiffness, const float *damping);
+int shard_set_material_ids(edynhip_ctx *c, uint32_t first, uint32_t n, const uint32_t *ids);
+int shard_insert_material_mixing(edynhip_ctx *c, uint32_t id0, uint32_t id1, const float *material6);
+int shard_reset_material_mixing(edynhip_ctx *c);
+int shard_ensure_extras_storage(edynhip_ctx *c);
 // world_records.hip: the registry records (edynhip_body_record) of the bodies this shard reports (`answers`), stored at their global
 // indices into records[num_bodies] - the world's pinned slot, mapped into this device
 int shard_pack_records(edynhip_ctx *c, const uint32_t *local_ids_dev, uint32_t n_local, uint32_t num_bodies, float present_dt, void *records);

@@ -24,7 +24,7 @@
 // are plain C++ in world_rules.hpp. What touches a device is split by concern, with what the files share in multi.hpp: this file holds the
 // world's life cycle, the scene description, the first build, the step and the plain getters; multi_shard.hip one shard's context and
 // its traffic; multi_partition.hip the monitor kernels, the approach check and the re-partition; multi_edit.hip the edits of a running
-// world; multi_records.hip the record hand-over; multi_query.hip the queries.
+// world; multi_materials.hip materials and the mix table; multi_records.hip the record hand-over; multi_query.hip the queries.
 #include "multi.hpp"
 
 using namespace eh;
@@ -130,6 +130,9 @@ void scene_append_bodies(edynhip_world *w, uint32_t k, const edynhip_bodies *in)
     opt(sc.gravity, in->gravity, 3, w->cfg.gravity);
     opt(sc.sleeping_disabled, in->sleeping_disabled, 1, &zero8);
     opt(sc.com, in->center_of_mass, 3, zeros);
+    // new bodies come with the default material and no material id (multi_materials.hip)
+    if (!sc.mat_extras.empty()) for (uint32_t i = 0; i < k; ++i) sc.mat_extras.insert(sc.mat_extras.end(), {0.0f, 0.0f, kMaterialLarge, kMaterialLarge});
+    if (!sc.mat_id.empty()) sc.mat_id.resize(n0 + k, kUnassignedMaterial);
     sc.n += k;
     w->removed.resize(sc.n, 0);
     w->stats.num_bodies = sc.n;
@@ -219,6 +222,7 @@ int edynhip_world_set_bodies(edynhip_world *w, uint32_t n, const edynhip_bodies 
     sc.kind.clear(); sc.shape_type.clear(); sc.pos.clear(); sc.orn.clear(); sc.linvel.clear(); sc.angvel.clear(); sc.mass.clear(); sc.shape_param.clear();
     sc.friction.clear(); sc.restitution.clear(); sc.inertia.clear(); sc.has_inertia.clear(); sc.group.clear(); sc.mask.clear(); sc.gravity.clear();
     sc.sleeping_disabled.clear(); sc.com.clear();
+    sc.mat_extras.clear(); sc.mat_id.clear(); w->extras_seen = false;   // (the mix table is not the bodies': it stays, as on one context)
     scene_append_bodies(w, n, in);
     sc.nj = 0; sc.jtype.clear(); sc.jbody.clear(); sc.jpivot.clear(); sc.jaxis.clear(); sc.jparams.clear(); sc.jalive.clear(); sc.defs.clear(); sc.exclusions.clear();
     w->removed.assign(n, 0); w->pending_tombs.clear();

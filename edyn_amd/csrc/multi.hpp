@@ -1,5 +1,5 @@
-// What the files of the multi-device world (multi.hip, multi_shard.hip, multi_partition.hip, multi_edit.hip, multi_records.hip,
-// multi_query.hip) share: the world and its shards, what travels through a re-partition, the error macros, and the functions that cross a
+// What the files of the multi-device world (multi.hip, multi_shard.hip, multi_partition.hip, multi_edit.hip, multi_materials.hip,
+// multi_records.hip, multi_query.hip) share: the world and its shards, what travels through a re-partition, the error macros, and the functions that cross a
 // file boundary. Internal: nothing here is part of the C-ABI.
 #pragma once
 #include "ctx.hpp"
@@ -39,6 +39,12 @@ struct HostScene {   // deep copy of what the caller described, in global indice
     std::vector<std::array<uint32_t, 2>> exclusions;
     struct Mesh { std::vector<float> v; std::vector<uint32_t> idx, faces; uint32_t flags; };
     std::vector<Mesh> meshes;
+    // materials (multi_materials.hip), each empty until it is first set: per body spin, roll, stiffness, damping; per body the material id
+    // (0xFFFF = unassigned); the mix table as the ordered list of insertions (id0, id1, material6), replayed on every context that is built
+    std::vector<float> mat_extras;
+    std::vector<uint32_t> mat_id;
+    struct MixEntry { uint32_t id0, id1; float m[6]; };
+    std::vector<MixEntry> mix;
 };
 
 // What a shard holds on its device for as long as its context lives. Owners release on the device that is current, so these are given up
@@ -61,6 +67,9 @@ struct ShardResources {
     // the shard holds; the step's events in global indices (device, [event_cap]); the point ids of `manifolds` as [m][4] on the device
     PinnedBuf<uint32_t> ev_cnt_host; uint32_t ev_held = 0;
     GrowBuf ev_out, pid_buf;
+    // materials: the point extras of `manifolds` as [m][4][2] float4 rows (world_rules.hpp) on the device, and pinned: what a collect
+    // read (Shard::xrows of them) until build_shard writes the rows it injects there
+    GrowBuf xtr_buf; PinnedBuf<float> xtr_host; size_t xtr_host_cap = 0;
     // record hand-over (edynhip_world_snapshot_records): per pinned slot the event that completes this shard's pack, and whether one is out
     Event rec_ev[2];
     bool rec_pending[2] = {false, false};
@@ -84,6 +93,7 @@ struct Shard {   // (move-only: its resources are)
     std::vector<uint32_t> sleep_label; std::vector<double> sleep_since; double sleep_clock = 0;
     std::vector<uint32_t> q_ignore;       // queries: the caller's ignore list in local indices
     std::vector<uint64_t> pids;           // contact events: the point ids of `manifolds` as [m][4]
+    size_t xrows = 0;                     // materials: how many of `manifolds` have their extras row in res.xtr_host, [m][32] (world_rules.hpp); 0 or all
 };
 
 class Pool {   // one persistent host thread per shard (a context is single-threaded; its step spins on its own counters)
@@ -181,6 +191,10 @@ struct edynhip_world {   // (the member order keeps `pool` - the shards' threads
     edynhip_params params{};
     edynhip_world_edit_stats edit_stats{};
     bool is_removed(uint32_t g) const { return g < removed.size() && removed[g] != 0; }
+    // materials: some body has had a contact_extras material since the scene was described (points mixed from it may live on after the
+    // material is gone) - with the mix table's entries what decides whether a re-partition carries the points' extras
+    bool extras_seen = false;
+    bool carries_extras() const { return eh::extras_carry_needed(extras_seen, scene.mix.size()); }
     // record hand-over (edynhip_world_snapshot_records / _map): two pinned slots used alternately, each [records: body_cap x 96 B | events:
     // ev_cap x 24 B], allocated portable and mapped so that every shard's device stores its records into them; what the slot holds; the home
     // device's side stream and per slot the event that completes the copy of the event block; the events that OCCURRED in the last
@@ -285,6 +299,9 @@ struct Carry {   // what travels with the islands through a re-partition (global
     // contact events: the ids of the carried points by body pair (body[0] << 32 | body[1], global) - a rebuilt shard puts them back over the
     // ids edynhip_set_manifolds issues, so a point keeps its id whichever shards it lives on
     std::unordered_map<uint64_t, std::array<uint64_t, 4>> point_ids;
+    // materials: the extras rows of the carried points by the same key (world_rules.hpp: the row layout) - a rebuilt shard puts them back over
+    // what edynhip_set_manifolds mixed from today's materials. Empty in a world without materials (extras_carry_needed).
+    std::unordered_map<uint64_t, std::array<float, kExtrasRowFloats>> point_extras;
 };
 
 // developer aid (EDYNHIP_WORLD_TRACE=1): wall time of the phases of a re-partition, to stderr
@@ -331,8 +348,9 @@ EH_LOCAL void free_shard(Shard &s);
 EH_LOCAL void upload_query_tables(edynhip_world *w, uint32_t r, uint32_t l0, const std::vector<uint32_t> *island = nullptr);
 EH_LOCAL void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_state);
 EH_LOCAL void gather_shard(edynhip_world *w, uint32_t r, bool with_growth);
-EH_LOCAL void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy);
-EH_LOCAL void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::vector<uint64_t> *ids = nullptr);
+EH_LOCAL void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy, bool extras = false);
+EH_LOCAL void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::vector<uint64_t> *ids = nullptr, std::vector<float> *extras = nullptr);
+EH_LOCAL void apply_materials(edynhip_world *w, Shard &s);
 // multi_partition.hip: the approach check and the re-partition
 EH_LOCAL int approach_check(edynhip_world *w, bool &close, bool per_body = false, const std::vector<IslandBox> *host_boxes = nullptr);
 EH_LOCAL int rebuild(edynhip_world *w, const Carry &carry, bool from_state, const std::vector<uint8_t> *only = nullptr);

@@ -101,6 +101,17 @@ void carry_point_ids(const Shard &s, Carry &carry) {
     }
 }
 
+// materials: the extras rows of a collected shard's points go with the re-partition, by global body pair like the ids
+void carry_point_extras(const Shard &s, Carry &carry) {
+    if (s.manifolds.empty() || s.xrows != s.manifolds.size()) return;
+    for (size_t k = 0; k < s.manifolds.size(); ++k) {
+        const edynhip_manifold &m = s.manifolds[k];
+        std::array<float, kExtrasRowFloats> row;
+        std::memcpy(row.data(), s.res.xtr_host + kExtrasRowFloats * k, sizeof(row));   // (straight from the pinned rows the collect read)
+        carry.point_extras[((uint64_t)s.local_ids[m.body[0]] << 32) | s.local_ids[m.body[1]]] = row;
+    }
+}
+
 // the applied impulses and tracked angles of a collected shard's joints go with the re-partition, by global joint
 void carry_joint_impulses(const Shard &s, Carry &carry) {
     for (uint32_t lj = 0; lj < s.local_joints.size() && !s.imp24.empty(); ++lj) {
@@ -179,7 +190,7 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
     // removal and a rebuilding edit with no step in between)
     if (from_edit && !w->pending_tombs.empty()) sticky = false;
     PhaseTrace trace(w, sticky ? "sticky re-partition" : "full re-partition");
-    w->pool->run([w, sticky](uint32_t r) { collect_shard(w, r, true, !sticky); });
+    w->pool->run([w, sticky](uint32_t r) { collect_shard(w, r, true, !sticky, w->carries_extras()); });
     EH_TRY(shard_error(w));
     trace.mark("collect light state of every shard");
     std::vector<uint32_t> labels(n);
@@ -226,6 +237,7 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
             Shard &s = w->shards[r];
             if (only && !(*only)[r]) { s.manifolds.clear(); continue; }
             carry_point_ids(s, carry);
+            carry_point_extras(s, carry);
             for (const edynhip_manifold &m : s.manifolds) {   // weight = 1 + the contact points the body takes part in (balance the rows)
                 const uint32_t a = s.local_ids[m.body[0]], b = s.local_ids[m.body[1]];
                 if (w->rank_of[a] == (int32_t)r) weights[a] += m.num_points;
@@ -247,6 +259,7 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
     ++w->stats.repartitions;
     trace.mark("island boxes, welding");
     if (!sticky) {
+        if (!carry.point_extras.empty()) ++w->stats.extras_carries;
         w->rank_of.assign(n, -1);
         partition_islands_spatial(n, welded.data(), sc.kind.data(), weights.data(), aabb.data(), W, w->rank_of.data());
         return rebuild(w, carry, true);
@@ -266,10 +279,10 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
         return EDYNHIP_OK;
     }
     trace.mark("sticky targets");
-    w->pool->run([w, &changed](uint32_t r) { if (changed[r]) collect_shard(w, r, false, true); });
+    w->pool->run([w, &changed](uint32_t r) { if (changed[r]) collect_shard(w, r, false, true, w->carries_extras()); });
     EH_TRY(shard_error(w));
     trace.mark("collect manifolds / joint impulses of the changed shards");
-    for (uint32_t r = 0; r < W; ++r) if (changed[r]) { carry_point_ids(w->shards[r], carry); carry_joint_impulses(w->shards[r], carry); }
+    for (uint32_t r = 0; r < W; ++r) if (changed[r]) { carry_point_ids(w->shards[r], carry); carry_point_extras(w->shards[r], carry); carry_joint_impulses(w->shards[r], carry); }
     // Manifolds: a body that stays in its shard keeps its place among the others that stay (local indices ascend with the global ones), so
     // the manifolds that stay ARE in canonical order already; only those whose island moves are taken out, sorted among themselves and
     // merged into their new shard's list. No global sort, one copy per record at most (the merged, sorted list of every changed shard's
@@ -306,6 +319,7 @@ int repartition(edynhip_world *w, bool sticky, const std::vector<std::array<uint
         s.manifolds.clear(); s.manifolds.shrink_to_fit();
     });
     trace.mark("sort out the carried manifolds per new shard");
+    if (!carry.point_extras.empty()) ++w->stats.extras_carries;
     carry.island_boxes = boxes;
     w->rank_of = next;
     const int rc_rebuild = rebuild(w, carry, true, &changed);

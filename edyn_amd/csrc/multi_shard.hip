@@ -38,6 +38,7 @@ void free_shard(Shard &s) {
     if (s.ctx) edynhip_destroy(s.ctx);
     s.ctx = nullptr;
     s.cap = s.joint_cap = s.meshes_created = 0;
+    s.xrows = 0;
 }
 
 // The world's query tables of shard r from local index l0 onwards (0: a shard just built; otherwise bodies [l0, nl) were appended to
@@ -66,6 +67,33 @@ void upload_query_tables(edynhip_world *w, uint32_t r, uint32_t l0, const std::v
         SH_HIP(s, hipMemcpy(s.res.qisl_dev + l0, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     shard_set_answers(s.ctx, r != 0 ? s.res.ans_dev : nullptr, std::move(bits), labels ? s.res.qisl_dev : nullptr);
+}
+
+// The world's materials of the bodies a context has just been given (and with them the default materials), and the mix table, as the
+// single context's calls would have set them. Bodies without a contact_extras material set none: a shard none of whose bodies has one
+// keeps its fast schedule (every schedule computes the same bits, include/edynhip.h "solve_schedule"). The table was emptied before
+// the bodies went up (build_shard): the insertions are replayed, in their order, into none.
+void apply_materials(edynhip_world *w, Shard &s) {
+    const HostScene &sc = w->scene;
+    const uint32_t nl = (uint32_t)s.local_ids.size();
+    if (nl && !sc.mat_extras.empty()) {
+        std::vector<float> col[4];
+        bool any = false;
+        for (int d = 0; d < 4; ++d) col[d].resize(nl);
+        for (uint32_t l = 0; l < nl; ++l) {
+            const float *m = &sc.mat_extras[4 * (size_t)s.local_ids[l]];
+            for (int d = 0; d < 4; ++d) col[d][l] = m[d];
+            any = any || !material_extras_default(m[0], m[1], m[2], m[3]);
+        }
+        if (any) SH_TRY(s, shard_set_material_extras(s.ctx, 0, nl, col[0].data(), col[1].data(), col[2].data(), col[3].data()));
+    }
+    if (nl && !sc.mat_id.empty()) {
+        std::vector<uint32_t> ids(nl);
+        bool any = false;
+        for (uint32_t l = 0; l < nl; ++l) { ids[l] = sc.mat_id[s.local_ids[l]]; any = any || ids[l] != kUnassignedMaterial; }
+        if (any) SH_TRY(s, shard_set_material_ids(s.ctx, 0, nl, ids.data()));
+    }
+    for (const HostScene::MixEntry &e : sc.mix) SH_TRY(s, shard_insert_material_mixing(s.ctx, e.id0, e.id1, e.m));
 }
 
 // (Re)builds shard r for the partition w->rank_of from the scene, the current global state and what the islands carry.
@@ -150,6 +178,9 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
     whole.sleeping_disabled = data_or_null(sc.sleeping_disabled); whole.center_of_mass = data_or_null(sc.com);
     const BodyRows mine(whole, s.local_ids);
     const edynhip_bodies b = mine.view();
+    // (a kept context still holds the mix table: emptied before the bodies go up, so that what edynhip_set_bodies derives from it - the
+    // restitution solver's switch - and the replay in apply_materials start from none)
+    SH_TRY(s, shard_reset_material_mixing(s.ctx));
     SH_TRY(s, edynhip_set_bodies(s.ctx, nl, &b));
     trace.mark("take + edynhip_set_bodies");
     if (from_state && !mine.com.empty()) {   // set_bodies read `pos` as the origin of bodies with an offset: put the centre-of-mass state back ...
@@ -159,6 +190,8 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
         // the derivation skips sleeping bodies
         SH_TRY(s, edynhip_refresh_derived(s.ctx));
     }
+    apply_materials(w, s);
+    if (s.rc != EDYNHIP_OK) return;
     // joints, in local indices
     const uint32_t njl = (uint32_t)s.local_joints.size();
     if (njl) {
@@ -199,6 +232,26 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
                 std::memcpy(&mine_ids[4 * k], it->second.data(), 4 * sizeof(uint64_t));
             }
         }
+        // materials: the carried points keep the mix they were created with and the impulses of their rolling and spinning rows
+        const bool with_extras = !carry.point_extras.empty() && !mine.empty();
+        if (with_extras) {
+            const size_t floats = kExtrasRowFloats * mine.size();
+            if (s.res.xtr_host_cap < floats) { s.res.xtr_host_cap = 0; SH_HIP(s, s.res.xtr_host.alloc(floats + floats / 2)); s.res.xtr_host_cap = floats + floats / 2; }
+            bool plain = true;
+            for (size_t k = 0; k < mine.size(); ++k) {
+                float *row = s.res.xtr_host + kExtrasRowFloats * k;
+                const auto it = carry.point_extras.find(((uint64_t)mine[k].body[0] << 32) | mine[k].body[1]);
+                if (it == carry.point_extras.end()) {
+                    s.rc = EDYNHIP_ERR_INTERNAL; s.err = "a carried manifold (bodies " + std::to_string(mine[k].body[0]) + ", " + std::to_string(mine[k].body[1]) + ") has no point extras";
+                    return;
+                }
+                std::memcpy(row, it->second.data(), sizeof(it->second));
+                plain = plain && extras_row_is_default(row, mine[k].num_points);
+            }
+            // (a point may outlive its bodies' materials: a context that no material of this build has put on the extras schedule - it may
+            // still own the storage from an earlier one - is put there for such a point)
+            if (!plain) SH_TRY(s, shard_ensure_extras_storage(s.ctx));
+        }
         for (edynhip_manifold &m : mine) { m.body[0] = (uint32_t)s.to_local[m.body[0]]; m.body[1] = (uint32_t)s.to_local[m.body[1]]; }   // a monotone map: the canonical order is kept
         trace.mark("joints, exclusions, select carried manifolds");
         if (!mine.empty()) SH_TRY(s, edynhip_set_manifolds(s.ctx, mine.data(), (uint32_t)mine.size()));
@@ -207,6 +260,13 @@ void build_shard(edynhip_world *w, uint32_t r, const Carry &carry, bool from_sta
             SH_HIP(s, hipMemcpyAsync(s.res.pid_buf.h, mine_ids.data(), mine_ids.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s.ctx->stream));
             SH_TRY(s, shard_inject_point_ids(s.ctx, (const uint64_t *)s.res.pid_buf.h, (uint32_t)mine.size()));
             SH_HIP(s, hipStreamSynchronize(s.ctx->stream));   // (mine_ids is read by the copy until here)
+        }
+        if (with_extras && shard_has_extras_storage(s.ctx)) {
+            const size_t bytes = kExtrasRowFloats * mine.size() * sizeof(float);
+            SH_HIP(s, s.res.xtr_buf.grow(bytes));
+            SH_HIP(s, hipMemcpyAsync(s.res.xtr_buf.h, s.res.xtr_host, bytes, hipMemcpyHostToDevice, s.ctx->stream));
+            SH_TRY(s, shard_inject_point_extras(s.ctx, s.res.xtr_buf.h, (uint32_t)mine.size()));
+            SH_HIP(s, hipStreamSynchronize(s.ctx->stream));   // (the pinned rows are rewritten by the next collect)
         }
         trace.mark("edynhip_set_manifolds");
         if (njl && !carry.imp24.empty()) {
@@ -280,12 +340,12 @@ void gather_shard(edynhip_world *w, uint32_t r, bool with_growth) {
 // What the islands carry, per shard, in two parts: LIGHT - island labels, AABBs, sleeping tags and timers (28-45 bytes per body: what a
 // re-partition decides on) - and HEAVY - the manifolds with their warm-start impulses and the joints' applied impulses (336 bytes per
 // manifold: only worth reading from the shards that are rebuilt).
-void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy) {
+void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy, bool extras) {
     Shard &s = w->shards[r];
     if (s.rc != EDYNHIP_OK) return;
     const uint32_t nl = (uint32_t)s.local_ids.size();
     if (light) { s.labels.assign(nl, 0); s.aabb.assign((size_t)nl * 6, 0.f); s.asleep.assign(nl, 0); }
-    s.manifolds.clear(); s.imp24.clear(); s.imp10.clear(); s.pids.clear();
+    s.manifolds.clear(); s.imp24.clear(); s.imp10.clear(); s.pids.clear(); s.xrows = 0;
     if (nl == 0) return;
     SH_HIP(s, hipSetDevice(s.device));
     if (light) {
@@ -309,6 +369,18 @@ void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy) {
         SH_HIP(s, hipMemcpyAsync(s.pids.data(), s.res.pid_buf.h, s.pids.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s.ctx->stream));
         SH_HIP(s, hipStreamSynchronize(s.ctx->stream));
     }
+    if (nm && extras) {   // materials: the points' extras travel with the records, [m][32] in the same order, in the shard's pinned buffer
+        const size_t floats = kExtrasRowFloats * (size_t)nm;
+        if (s.res.xtr_host_cap < floats) { s.res.xtr_host_cap = 0; SH_HIP(s, s.res.xtr_host.alloc(floats + floats / 2)); s.res.xtr_host_cap = floats + floats / 2; }
+        if (shard_has_extras_storage(s.ctx)) {
+            SH_HIP(s, s.res.xtr_buf.grow(floats * sizeof(float)));
+            SH_TRY(s, shard_gather_point_extras(s.ctx, s.res.xtr_buf.h));
+            SH_HIP(s, hipMemcpyAsync(s.res.xtr_host, s.res.xtr_buf.h, floats * sizeof(float), hipMemcpyDeviceToHost, s.ctx->stream));
+            SH_HIP(s, hipStreamSynchronize(s.ctx->stream));
+        } else   // (no material has reached this context: its points are plain)
+            for (uint32_t k = 0; k < nm; ++k) extras_row_default(s.res.xtr_host + kExtrasRowFloats * (size_t)k, s.manifolds[k].num_points);
+        s.xrows = nm;
+    }
     const uint32_t njl = (uint32_t)s.local_joints.size();
     if (njl) {
         s.imp24.assign((size_t)njl * 24, 0.f); s.imp10.assign((size_t)njl * 10, 0.f);
@@ -318,16 +390,17 @@ void collect_shard(edynhip_world *w, uint32_t r, bool light, bool heavy) {
 }
 
 // gathers the manifolds of all shards, each once, global indices, canonical order; ids (or nullptr): their points' ids [m][4], in that order
-void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::vector<uint64_t> *ids) {
+void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::vector<uint64_t> *ids, std::vector<float> *extras) {
     out.clear();
     std::vector<const uint64_t *> from;   // per gathered record: its row of the shard's id table
+    std::vector<const float *> xfrom;     // ... and of its extras table
     for (uint32_t r = 0; r < w->shards.size(); ++r) {
         Shard &s = w->shards[r];
         for (size_t k = 0; k < s.manifolds.size(); ++k) {
             edynhip_manifold m = s.manifolds[k];
             m.body[0] = s.local_ids[m.body[0]]; m.body[1] = s.local_ids[m.body[1]];
             const int32_t ra = w->rank_of[m.body[0]], rb = w->rank_of[m.body[1]];
-            if (ra == (int32_t)r || (ra < 0 && rb == (int32_t)r)) { out.push_back(m); if (ids) from.push_back(s.pids.size() == 4 * s.manifolds.size() ? &s.pids[4 * k] : nullptr); }
+            if (ra == (int32_t)r || (ra < 0 && rb == (int32_t)r)) { out.push_back(m); if (ids) from.push_back(s.pids.size() == 4 * s.manifolds.size() ? &s.pids[4 * k] : nullptr); if (extras) xfrom.push_back(s.xrows == s.manifolds.size() ? s.res.xtr_host + kExtrasRowFloats * k : nullptr); }
         }
     }
     // canonical order: sort (key, position) pairs and move every 336-byte record once (a stable sort of the records themselves, with
@@ -341,6 +414,14 @@ void merge_manifolds(edynhip_world *w, std::vector<edynhip_manifold> &out, std::
     if (ids) {
         ids->assign(4 * out.size(), 0);
         for (uint32_t k = 0; k < out.size(); ++k) if (const uint64_t *row = from[order[k].second]) std::memcpy(&(*ids)[4 * (size_t)k], row, 4 * sizeof(uint64_t));
+    }
+    if (extras) {   // (a world without materials gathers no rows: every point is plain)
+        extras->resize(kExtrasRowFloats * out.size());
+        for (uint32_t k = 0; k < out.size(); ++k) {
+            float *dst = &(*extras)[kExtrasRowFloats * (size_t)k];
+            if (const float *row = xfrom[order[k].second]) std::memcpy(dst, row, kExtrasRowFloats * sizeof(float));
+            else extras_row_default(dst, out[k].num_points);
+        }
     }
 }
 

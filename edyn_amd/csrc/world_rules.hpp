@@ -376,4 +376,53 @@ static inline bool shard_holds_exclusion(int32_t ra, int32_t rb, uint32_t r) {
     return shard_holds_body(ra, r) && shard_holds_body(rb, r) && (ra == (int32_t)r || rb == (int32_t)r);
 }
 
+// ------------------------------------------------------------------------------------------------ materials
+// contact_extras materials, material ids and the mix table on a multi-device world (multi_materials.hip). What a contact point carries
+// beyond edynhip_manifold - its material as mixed at creation and the warm-start impulses of its rolling pair and spinning row - travels
+// through a re-partition as one 128-byte row per manifold: row[2 k .. 2 k + 1] of point k = (roll, spin, stiffness, damping),
+// (rolling impulse 0, 1, spin impulse, -), four floats each; the slots at or beyond the manifold's point count are all zero.
+constexpr float kMaterialLarge = 1e18f;        // large_scalar: the default stiffness and damping (dmath.hpp kLarge)
+constexpr uint32_t kUnassignedMaterial = 0xFFFFu;
+constexpr uint32_t kExtrasRowFloats = 32;
+// material::{spin_friction, roll_friction, stiffness, damping} as a body is created with them (comp/material.hpp:15-22)
+static inline bool material_extras_default(float spin, float roll, float stiffness, float damping) {
+    return !(spin > 0) && !(roll > 0) && !(stiffness < kMaterialLarge) && !(damping < kMaterialLarge);
+}
+static inline bool material_extras_valid(float spin, float roll, float stiffness, float damping) {
+    return !(spin < 0) && !(roll < 0) && stiffness > 0 && damping > 0;
+}
+// The row of a manifold whose context keeps no extras: every living point has the default material and no impulses.
+static inline void extras_row_default(float *row, uint32_t num_points) {
+    for (uint32_t i = 0; i < kExtrasRowFloats; ++i) row[i] = 0.0f;
+    for (uint32_t k = 0; k < num_points && k < 4; ++k) { row[8 * k + 2] = kMaterialLarge; row[8 * k + 3] = kMaterialLarge; }
+}
+// ... and whether a row says no more than that: a shard that is given only such rows needs no extras storage of its own.
+static inline bool extras_row_is_default(const float *row, uint32_t num_points) {
+    for (uint32_t k = 0; k < num_points && k < 4; ++k) {
+        const float *p = row + 8 * k;
+        if (p[0] != 0 || p[1] != 0 || p[2] != kMaterialLarge || p[3] != kMaterialLarge || p[4] != 0 || p[5] != 0 || p[6] != 0) return false;
+    }
+    return true;
+}
+// edynhip_get_point_extras' 4 x 7 floats of a manifold from its row: rolling impulse[2], spin impulse, roll, spin, stiffness, damping
+static inline void extras_row_to_out7(const float *row, float *out28) {
+    for (uint32_t k = 0; k < 4; ++k) {
+        const float *p = row + 8 * k;
+        float *o = out28 + 7 * k;
+        o[0] = p[4]; o[1] = p[5]; o[2] = p[6]; o[3] = p[0]; o[4] = p[1]; o[5] = p[2]; o[6] = p[3];
+    }
+}
+// The shards that take an edit of the bodies [first, first + n): the owner of a dynamic body, every shard for a replicated one.
+// touched[W] (cleared first); rank_of as the partition has it.
+static inline void shards_of_body_range(const int32_t *rank_of, uint32_t first, uint32_t n, uint32_t W, uint8_t *touched) {
+    for (uint32_t r = 0; r < W; ++r) touched[r] = 0;
+    for (uint32_t i = first; i < first + n; ++i) {
+        if (rank_of[i] >= 0) { if ((uint32_t)rank_of[i] < W) touched[(uint32_t)rank_of[i]] = 1; }
+        else for (uint32_t r = 0; r < W; ++r) touched[r] = 1;
+    }
+}
+// A re-partition carries the points' extras once the world holds any contact_extras material or any mix-table entry: from then on a
+// point may have been created with a mix that today's materials would not give it again. A world without either carries nothing.
+static inline bool extras_carry_needed(bool any_extras_material_ever, size_t mix_entries) { return any_extras_material_ever || mix_entries != 0; }
+
 }  // namespace eh

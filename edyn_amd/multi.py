@@ -214,6 +214,33 @@ class MultiWorld:
         self._check(self._L.edynhip_world_get_manifolds(self._h, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
 
+    # ---- materials: World.set_material_extras / .set_material_ids / .insert_material_mixing / .get_point_extras on the whole world
+    def set_material_extras(self, first, spin=None, roll=None, stiffness=None, damping=None):
+        """material::{spin_friction, roll_friction, stiffness, damping} of bodies [first, first + n), global indices, before the first step
+        or on a running world (edynhip_world_set_material_extras). Arrays of equal length; None = the reference's default."""
+        arrs = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (spin, roll, stiffness, damping)]
+        n = max(len(a) for a in arrs if a is not None)
+        self._check(self._L.edynhip_world_set_material_extras(self._h, int(first), n, *[None if a is None else _ptr(a) for a in arrs]))
+
+    def set_material_ids(self, first, ids):
+        """material::id of bodies [first, first + len(ids)) (0xFFFF = unassigned): keys into the material mix table."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        self._check(self._L.edynhip_world_set_material_ids(self._h, int(first), len(a), _ptr(a)))
+
+    def insert_material_mixing(self, id0, id1, restitution=0.0, friction=0.5, spin=0.0, roll=0.0, stiffness=1e18, damping=1e18):
+        """edyn::insert_material_mixing on every shard: the material of contact points between bodies with these material ids."""
+        m = np.array([restitution, friction, spin, roll, stiffness, damping], np.float32)
+        self._check(self._L.edynhip_world_insert_material_mixing(self._h, int(id0), int(id1), _ptr(m)))
+
+    def get_point_extras(self):
+        """[num_manifolds, 4, 7]: rolling impulse 0/1, spin impulse, roll mu, spin mu, stiffness, damping (get_manifolds order)."""
+        m = C.c_uint32(0)
+        self._check(self._L.edynhip_world_get_point_extras(self._h, None, 0, C.byref(m)))
+        out = np.zeros((m.value, 4, 7), np.float32)
+        if m.value:
+            self._check(self._L.edynhip_world_get_point_extras(self._h, _ptr(out), m.value, C.byref(m)))
+        return out[:m.value]
+
     # ---- contact events: World.get_contact_events / .get_point_ids on the whole world (init_config(contact_events=True))
     def get_contact_events(self):
         """Events of the steps of the last step_simulation() call: structured array (type, step, body[2], point_id) as World returns it -

@@ -247,9 +247,13 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
     // (solver.cpp:408-428) across devices. Bodies of every shape, every constraint type, exclusions, settings, contact entities
     // (materialize_contacts, contact_point_data, edyn::refresh_contact_points, manifold_exists, visit_edges) and step callbacks in the
     // sequential modes are supported: the write-back reads the world's record hand-over in place (edynhip_world_snapshot_records), so
-    // state, presentation, sleeping tags and contact events arrive as they do from one device. Still single-device features (a
-    // stepper_error EDYNHIP_ERR_UNSUPPORTED when combined): execution_mode::asynchronous, contact_extras materials, material ids and
-    // the mix table, edyn::raycast and the AABB queries. An edit of a running multi-device world is forwarded to
+    // state, presentation, sleeping tags and contact events arrive as they do from one device. `material` with its contact_extras fields
+    // (rolling / spinning friction, soft contacts), material::id and edyn::insert_material_mixing go to the world as they go to one
+    // context (edynhip.h edynhip_world_set_material_extras ...), also for bodies made and table entries inserted while the world runs: a
+    // contact point keeps the material it was created with, and its rolling and spinning impulses, wherever its island goes; a material
+    // edited on a running world goes up in place after edyn::refresh<edyn::material>(registry, entity). Still
+    // single-device features (a stepper_error EDYNHIP_ERR_UNSUPPORTED when combined): execution_mode::asynchronous, edyn::raycast and
+    // the AABB queries. An edit of a running multi-device world is forwarded to
     // the world as it is to one context (edynhip.h "Edits of a RUNNING multi-device world"): bodies and constraints made after attach,
     // their definitions, exclude_collision, registry.destroy of either, edyn::refresh and settings changes keep every contact's warm
     // start, the joints' impulses and angles, sleep timers and the step count - the registry program computes what it computes on one
@@ -480,6 +484,7 @@ struct gpu_stepper {
     void (*post_step)(entt::registry &){nullptr};
     struct mixing { uint32_t id0, id1; float v[6]; };
     std::vector<mixing> mixings;   // insert_material_mixing calls, replayed into a (re)created context
+    std::vector<uint32_t> material_dirty;   // edyn::refresh<material>(registry, entity): bodies whose contact_extras fields / id changed (flush_materials)
     bool refresh_friction{false};  // set_rigidbody_friction: the carried contact points take the bodies' current materials (rigidbody.cpp:324-350)
     std::vector<std::pair<std::shared_ptr<convex_mesh>, uint32_t>> meshes;   // convex meshes the current device context holds, with their ids
     std::vector<uint32_t> reshaped;   // bodies whose shape / kind changed: their contacts are detected afresh by the re-created context
@@ -698,7 +703,6 @@ inline void upload_joint_defs(entt::registry &registry, gpu_stepper &s, uint32_t
 inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     const uint32_t total = (uint32_t)s.bodies.size(), nj = (uint32_t)s.constraints.size();
     if (s.world) { edynhip_world_destroy(s.world); s.world = nullptr; s.contacts_resync = true; }   // a new world issues new point ids: the contact entities are rebuilt
-    if (!s.mixings.empty()) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: the material mix table is a single-device feature (init_config::devices)");
     edynhip_config c{};
     c.max_manifolds = s.cfg.max_manifolds;
     c.fixed_dt = s.cfg.fixed_dt;
@@ -727,9 +731,12 @@ inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
         }
         return id;
     });
-    if (A.any_extras || A.any_ids) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: contact_extras materials and material ids are single-device features (init_config::devices)");
     const edynhip_bodies b = A.view();   // destroyed bodies went up as shapeless static placeholders: they take part in nothing
     check(s, edynhip_world_set_bodies(s.world, total, &b));
+    // materials, in the order the single-device upload gives them to its context (upload_scene): extras, the mix table, ids
+    if (A.any_extras) check(s, edynhip_world_set_material_extras(s.world, 0, total, A.xspin.data(), A.xroll.data(), A.xstiff.data(), A.xdamp.data()));
+    for (auto &m : s.mixings) check(s, edynhip_world_insert_material_mixing(s.world, m.id0, m.id1, m.v));   // a (re)created world
+    if (A.any_ids) check(s, edynhip_world_set_material_ids(s.world, 0, total, A.mat_ids.data()));
     std::vector<int32_t> jt; std::vector<uint32_t> jb; std::vector<float> jp, ja, jq;
     std::vector<uint32_t> dead_joints;
     joint_arrays(registry, s, 0, jt, jb, jp, ja, jq, dead_joints);
@@ -764,10 +771,11 @@ inline void append_scene_multi(entt::registry &registry, gpu_stepper &s) {
             for (auto &known : s.meshes) if (known.first == ph.mesh) id = known.second;
             return id;
         });
-        if (A.any_extras || A.any_ids) throw stepper_error(EDYNHIP_ERR_UNSUPPORTED, "edyn: contact_extras materials and material ids are single-device features (init_config::devices)");
         const edynhip_bodies b = A.view();
         uint32_t first_index = 0;
         check(s, edynhip_world_add_bodies(s.world, n, &b, &first_index));
+        if (A.any_extras) check(s, edynhip_world_set_material_extras(s.world, first, n, A.xspin.data(), A.xroll.data(), A.xstiff.data(), A.xdamp.data()));
+        if (A.any_ids) check(s, edynhip_world_set_material_ids(s.world, first, n, A.mat_ids.data()));
         if (!A.dead.empty()) check(s, edynhip_world_remove_bodies(s.world, (uint32_t)A.dead.size(), A.dead.data()));
         s.uploaded_bodies = total;
     }
@@ -790,6 +798,28 @@ inline void append_scene_multi(entt::registry &registry, gpu_stepper &s) {
     for (size_t k = s.exclusions_uploaded; k < s.exclusions.size(); ++k) check(s, edynhip_world_edit_exclusion(s.world, s.exclusions[k][0], s.exclusions[k][1], 1));
     s.exclusions_uploaded = s.exclusions.size();
     s.scene_dirty = false;
+}
+
+// edyn::refresh<material>: the contact_extras fields and the id of a body that is already on the device go to its context - or to the
+// multi-device world - in place, as registry.patch<material> reaches the reference's narrowphase: contact points made from then on mix
+// the new values, the living ones keep theirs. (A body that has not gone up yet takes its material with it; friction changes the living
+// points too and goes through set_rigidbody_friction.)
+inline void flush_materials(entt::registry &registry, gpu_stepper &s) {
+    for (const uint32_t i : s.material_dirty) {
+        if (i >= s.uploaded_bodies || s.bodies[i] == entt::null) continue;
+        const material *mt = registry.try_get<material>(s.bodies[i]);
+        if (!mt) continue;
+        const float spin = mt->spin_friction, roll = mt->roll_friction, stiff = mt->stiffness, damp = mt->damping;
+        const uint32_t id = mt->id;
+        if (s.world) {
+            check(s, edynhip_world_set_material_extras(s.world, i, 1, &spin, &roll, &stiff, &damp));
+            check(s, edynhip_world_set_material_ids(s.world, i, 1, &id));
+        } else if (s.ctx) {
+            check(s, edynhip_set_material_extras(s.ctx, i, 1, &spin, &roll, &stiff, &damp));
+            check(s, edynhip_set_material_ids(s.ctx, i, 1, &id));
+        }
+    }
+    s.material_dirty.clear();
 }
 
 constexpr uint32_t prefetch_events_max = 8192;   // contact events that travel ahead of a step's state (sequential modes); more = read after the step
@@ -1354,6 +1384,7 @@ inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsign
             phase_timer t(s.tm.upload);
             if (!s.world || s.recreate) upload_scene_multi(registry, s);
             else if (s.scene_dirty) append_scene_multi(registry, s);
+            if (!s.material_dirty.empty()) flush_materials(registry, s);
             if (s.state_dirty) upload_state(registry, s);
             apply_params(s);
         }
@@ -1381,6 +1412,7 @@ inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsign
     {
         phase_timer t(s.tm.upload);
         if (s.scene_dirty) upload_scene(registry, s);
+        if (!s.material_dirty.empty()) flush_materials(registry, s);
         if (s.state_dirty) upload_state(registry, s);   // also after an append: edits made in the same frame are not lost
         apply_params(s);
     }
@@ -1521,6 +1553,18 @@ using step_callback_t = void (*)(entt::registry &);
 inline void set_pre_step_callback(entt::registry &registry, step_callback_t func) { registry.ctx().get<detail::gpu_stepper>().pre_step = func; }
 inline void set_post_step_callback(entt::registry &registry, step_callback_t func) { registry.ctx().get<detail::gpu_stepper>().post_step = func; }
 inline void refresh(entt::registry &registry) { registry.ctx().get<detail::gpu_stepper>().state_dirty = true; }
+/// Tell the stepper that components of ONE rigid body were edited (registry.patch<Component> analogue). edyn::refresh<edyn::material>:
+/// the contact_extras fields (spin_friction, roll_friction, stiffness, damping) and the id go to the device in place before the next
+/// step - on one device and on init_config::devices alike, nothing is rebuilt; contact points made from then on mix the new values.
+/// Any other component: as edyn::refresh(registry).
+template <typename... Component>
+inline void refresh(entt::registry &registry, entt::entity entity) {
+    auto &s = registry.ctx().get<detail::gpu_stepper>();
+    if constexpr ((std::is_same_v<Component, material> || ...)) {
+        if (auto *bi = registry.try_get<detail::body_index>(entity)) s.material_dirty.push_back(bi->value);
+    }
+    if constexpr ((!std::is_same_v<Component, material> || ...)) s.state_dirty = true;
+}
 
 /// stepper_sequential::update (stepper_sequential.cpp:28-119): fixed-dt accumulator; when more steps are due than
 /// max_steps_per_update, the steps that do run carry stretched time stamps (:60-66; they feed the island sleep timers, the
@@ -2411,6 +2455,7 @@ inline void insert_material_mixing(entt::registry &registry, material::id_type i
     detail::gpu_stepper::mixing e{id0, id1, {m.restitution, m.friction, m.spin_friction, m.roll_friction, m.stiffness, m.damping}};
     s.mixings.push_back(e);
     if (s.ctx) detail::check(s, edynhip_insert_material_mixing(s.ctx, id0, id1, e.v));
+    if (s.world) detail::check(s, edynhip_world_insert_material_mixing(s.world, id0, id1, e.v));   // init_config::devices: every shard, in place
 }
 
 /// Refreshes pivots / normal / distance / impulses of every contact_point entity from the device (one read-back).

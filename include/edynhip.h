@@ -433,7 +433,8 @@ int edynhip_get_joint_slot_impulses(edynhip_ctx *ctx, float *impulses24);
  * from then on mix them (material_mixing.hpp:20-34) and, where a mixed value is not the default, get the rolling-friction
  * pair, the spinning-friction row and / or the force-limited ("soft") normal row of contact_extras_constraint
  * (contact_extras_constraint.cpp:12-110, constraint_row_spin_friction.cpp:5-36); soft contacts take no position
- * correction. A world with such materials solves on the per-colour schedule. roll_direction components are not modelled.
+ * correction. A world with such materials solves on the per-colour schedule. material::roll_direction is modelled: the tangent axes of
+ * the rolling pair of a dynamic capsule or cylinder are scaled by the projection of its axis (contact_extras_constraint.cpp:44-55).
  * edynhip_get_point_extras: out[4 * i + k][7] = rolling impulse[2], spin impulse, mixed roll / spin coefficient, stiffness,
  * damping of point k of manifold i in edynhip_get_manifolds order. */
 int edynhip_set_material_extras(edynhip_ctx *ctx, uint32_t first, uint32_t n, const float *spin_friction, const float *roll_friction,
@@ -649,6 +650,8 @@ typedef struct {
     uint32_t repartitions;           /* times the shards were rebuilt because islands of different shards met (or on request) */
     uint32_t bodies_per_shard[16];   /* bodies whose state each shard reports (shard 0 also reports the replicated ones) */
     uint32_t rebalances;             /* meetings that took the full, load-balanced re-partition because the heaviest shard exceeded 1.5 x the mean (ABI 15) */
+    uint32_t extras_carries;         /* re-partitions that carried the points' extras (materials, below); always 0 in a world without materials.
+                                        Appended at the end of the struct with edynhip_world_set_material_extras: no earlier field has moved */
 } edynhip_world_stats;
 edynhip_world *edynhip_world_create(const edynhip_config *cfg /* .device is ignored; capacities 0 = sized per shard */,
                                     const int32_t *devices, uint32_t num_devices, int *status_out);
@@ -679,7 +682,10 @@ int edynhip_world_get_partition(edynhip_world *w, int32_t *shard_of_body);   /* 
 int edynhip_world_repartition(edynhip_world *w);                             /* re-partition now (load balance / tests) */
 int edynhip_world_get_manifolds(edynhip_world *w, edynhip_manifold *out, uint32_t capacity, uint32_t *n);   /* global indices, canonical order */
 int edynhip_world_get_stats(edynhip_world *w, edynhip_world_stats *out);
-edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard);        /* a shard's context (read-only use: statistics, timings) */
+edynhip_ctx *edynhip_world_context(edynhip_world *w, uint32_t shard);        /* a shard's context (read-only use: statistics, timings).
+    Since the world has materials of its own (edynhip_world_set_material_extras, below) the four single-context material calls -
+    edynhip_set_material_extras / _set_material_ids / _insert_material_mixing / _get_point_extras - return EDYNHIP_ERR_UNSUPPORTED on it,
+    like the queries: read a world's point extras through edynhip_world_get_point_extras */
 
 /* edynhip_raycast / edynhip_query_aabb on a multi-device world (additive to ABI 15). Arguments, result layout, flags, capacity rules and
  * error codes are those of the single-context calls; every body index - the ignore list, hit.body, ids, island labels - is GLOBAL. The
@@ -769,6 +775,29 @@ int edynhip_world_set_state(edynhip_world *w, const float *pos, const float *orn
 int edynhip_world_get_params(edynhip_world *w, edynhip_params *out);
 int edynhip_world_set_params(edynhip_world *w, const edynhip_params *params);
 int edynhip_world_get_edit_stats(edynhip_world *w, edynhip_world_edit_stats *out);
+/* edynhip_set_material_extras / _set_material_ids / _insert_material_mixing / _get_point_extras on a multi-device world (additive to ABI 15):
+ * same arguments, same rules, GLOBAL body indices, before the first step or on a running world. The world returns, bit for bit, what ONE
+ * context holding the whole scene returns after the same calls and steps.
+ *   where     a body's material goes to the shard that owns it, a replicated (non-dynamic) body's to every shard, the mix table - the
+ *             insertions in the order they were made - to every shard; whatever builds or rebuilds a shard applies them again.
+ *   in place  on a running world the calls are forwarded to the shard contexts; no shard is rebuilt and nothing is re-partitioned
+ *             (edynhip_world_edit_stats counts them as in-place edits). As on one context only points created from then on see a change.
+ *   carry     a point's material as mixed at its creation and the impulses of its rolling pair and spinning row go with it through every
+ *             re-partition (sticky or full, rebuilt and kept contexts alike), gathered and put back on the shards' devices
+ *             (edyn_amd/csrc/world_extras.hip), once the world holds any such material or mix-table entry; edynhip_world_stats.extras_carries
+ *             counts these. A world without materials gathers, copies and allocates nothing for it.
+ *   schedule  a shard none of whose bodies has a contact_extras material keeps its fast solve schedule (every schedule computes the same bits).
+ *   reading   edynhip_world_get_point_extras: out7[4 * i + k][7] of point k of manifold i in edynhip_world_get_manifolds order; out7 == NULL
+ *             counts; capacity_manifolds < *n: EDYNHIP_ERR_CAPACITY (*n is set). edynhip_world_set_bodies resets the bodies' materials and
+ *             ids; the mix table stays, as on one context.
+ *   errors    a body range beyond num_bodies, ids above 0xFFFF, an unassigned id in a mix entry, negative friction or non-positive stiffness /
+ *             damping, a missing array: EDYNHIP_ERR_INVALID (edynhip_world_last_error); the world is left as it was.
+ * The public single-context calls refuse a shard context (edynhip_world_context) with EDYNHIP_ERR_UNSUPPORTED. */
+int edynhip_world_set_material_extras(edynhip_world *w, uint32_t first, uint32_t n, const float *spin_friction, const float *roll_friction,
+                                      const float *stiffness, const float *damping);
+int edynhip_world_set_material_ids(edynhip_world *w, uint32_t first, uint32_t n, const uint32_t *ids);
+int edynhip_world_insert_material_mixing(edynhip_world *w, uint32_t id0, uint32_t id1, const float *material6);
+int edynhip_world_get_point_extras(edynhip_world *w, float *out7, uint32_t capacity_manifolds, uint32_t *n);
 /* edynhip_get_asleep on the whole world (additive to ABI 15): asleep[num_bodies], every body's sleeping_tag from the shard that reports
  * its state; all 0 without EDYNHIP_FLAG_SLEEPING. (With tombstones in the world the partition no longer tells which bodies a shard holds.) */
 int edynhip_world_get_asleep(edynhip_world *w, uint8_t *asleep);
