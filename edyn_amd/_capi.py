@@ -107,6 +107,7 @@ class QueryAabbView(C.Structure):   # edynhip_query_aabb_view: a box ticket's li
 class RecordView(C.Structure):
     _fields_ = [("records", C.c_void_p), ("num_bodies", C.c_uint32), ("step_index", C.c_uint32), ("events", C.c_void_p),
                 ("num_events", C.c_uint32), ("total_events", C.c_uint32)]
+EDIT_MASS, EDIT_INERTIA, EDIT_MATERIAL, EDIT_SHAPE, EDIT_KIND = 1, 2, 4, 8, 16   # EDYNHIP_EDIT_*: the field groups of edynhip_edit_bodies
 STAGE_BROADPHASE, STAGE_NARROWPHASE, STAGE_ISLANDS, STAGE_SOLVE, STAGE_ALL = 1, 2, 4, 8, 15
 # EDYNHIP_PATH_* of include/edynhip.h (edynhip_debug_paths): name -> bit of the mask
 PATH_BITS = {"COMPACT_DIRECT": 1 << 0, "COMPACT_LIBRARY": 1 << 1, "SORT_DIRECT": 1 << 2, "SORT_LIBRARY": 1 << 3, "SPECULATE": 1 << 4,
@@ -125,7 +126,7 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_get_manifolds", "edynhip_set_manifolds", "edynhip_get_pairs", "edynhip_get_joint_impulses",
            "edynhip_get_timings", "edynhip_get_stats", "edynhip_abi_version", "edynhip_set_pair_filter", "edynhip_default_should_collide", "edynhip_debug_collide", "edynhip_add_bodies", "edynhip_get_asleep", "edynhip_wake_all", "edynhip_wake_bodies", "edynhip_set_center_of_mass",
            "edynhip_refresh_derived", "edynhip_exclude_collision", "edynhip_remove_collision_exclusion", "edynhip_add_joints",
-           "edynhip_remove_joints", "edynhip_set_joint_params", "edynhip_remove_bodies", "edynhip_get_params", "edynhip_set_params",
+           "edynhip_remove_joints", "edynhip_set_joint_params", "edynhip_remove_bodies", "edynhip_edit_bodies", "edynhip_get_params", "edynhip_set_params",
            "edynhip_step_timed", "edynhip_get_contact_events", "edynhip_get_point_ids", "edynhip_snapshot", "edynhip_snapshot_read", "edynhip_snapshot_records", "edynhip_snapshot_map", "edynhip_set_event_prefetch", "edynhip_prefetched_events",
            "edynhip_set_material_extras", "edynhip_get_point_extras", "edynhip_set_joint_definition",
            "edynhip_set_generic_definition", "edynhip_get_joint_slot_impulses", "edynhip_set_material_ids", "edynhip_insert_material_mixing",
@@ -228,6 +229,7 @@ def lib():
         L.edynhip_remove_joints.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_set_joint_params.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_remove_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.edynhip_edit_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Bodies), C.c_uint32]
         L.edynhip_get_params.argtypes = [C.c_void_p, C.POINTER(Params)]
         L.edynhip_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
         L.edynhip_step_timed.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.c_double]

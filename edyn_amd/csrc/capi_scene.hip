@@ -6,6 +6,7 @@
 #include "ctx_rules.hpp"
 #include "dstep.hpp"
 #include "dpolyhedron.hpp"
+#include "dbodyinit.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -34,62 +35,8 @@ __global__ void k_init_bodies(uint32_t first, uint32_t n, RawBodies r, Bodies b,
     if (kind == EDYNHIP_KIND_DYNAMIC) {
         const float mass = r.mass[l];
         inv_m = 1.0f / mass;
-        m3 I;
-        if (r.has_inertia && r.has_inertia[l]) {
-            const float *p = r.inertia + 9 * l;
-            I = {{p[0], p[1], p[2]}, {p[3], p[4], p[5]}, {p[6], p[7], p[8]}};
-        } else if (st == dc::SHAPE_BOX) {   // moment_of_inertia.cpp:11-17,179-181
-            f3 ext = from4(sp) * 2.0f;
-            f3 d = 1.0f / 12.0f * mass * mk3(ext.y * ext.y + ext.z * ext.z, ext.z * ext.z + ext.x * ext.x, ext.x * ext.x + ext.y * ext.y);
-            I = {{d.x, 0, 0}, {0, d.y, 0}, {0, 0, d.z}};
-        } else if (st == dc::SHAPE_SPHERE) {   // :19-21,163-165
-            float s = 0.4f * mass * sp.x * sp.x;
-            I = {{1 * s, 0 * s, 0 * s}, {0 * s, 1 * s, 0 * s}, {0 * s, 0 * s, 1 * s}};
-        } else if (st == dc::SHAPE_CAPSULE) {   // moment_of_inertia.cpp:65-90,171-173, shape_volume.cpp:10-16
-            const float kPiF = 3.1415926535897932384626433832795029f;
-            const float len = sp.y * 2, radius = sp.x;
-            const float cyl_vol = kPiF * radius * radius * len;
-            const float sph_vol = kPiF * radius * radius * radius * 4.0f / 3.0f;
-            const float total_vol = cyl_vol + sph_vol;
-            const float cyl_mass = mass * cyl_vol / total_vol, sph_mass = mass * sph_vol / total_vol;
-            const float cyl_xx = 0.5f * cyl_mass * radius * radius;
-            const float cyl_yy = 1.0f / 12.0f * cyl_mass * (3.0f * radius * radius + len * len);
-            const float sph_inertia = 0.4f * sph_mass * radius * radius;
-            // the capsule formula reads the cylinder's vector as (.x axial, .y transverse) although it arrives permuted for
-            // the axis (:77-81): reproduced - it is the inertia the reference simulates with
-            const f3 cyl = sp.z == 0.0f ? mk3(cyl_xx, cyl_yy, cyl_yy) : (sp.z == 1.0f ? mk3(cyl_yy, cyl_xx, cyl_yy) : mk3(cyl_yy, cyl_yy, cyl_xx));
-            const float xx = sph_inertia + cyl.x;
-            const float yy_zz = sph_inertia + sph_mass * square(4.0f * len + 3.0f * radius) / 64.0f + cyl.y;
-            const f3 d = sp.z == 0.0f ? mk3(xx, yy_zz, yy_zz) : (sp.z == 1.0f ? mk3(yy_zz, xx, yy_zz) : mk3(yy_zz, yy_zz, xx));
-            I = {{d.x, 0, 0}, {0, d.y, 0}, {0, 0, d.z}};
-        } else if (st == dc::SHAPE_CYLINDER) {   // moment_of_inertia.cpp:27-44,167-169
-            const f3 d = dc::cylinder_inertia_diag(dc::cyl_of(sp), mass);
-            I = {{d.x, 0, 0}, {0, d.y, 0}, {0, 0, d.z}};
-        } else if (st == dc::SHAPE_POLYHEDRON) {   // moment_of_inertia.cpp:93-157,183-185
-            I = dc::polyhedron_inertia(meshes, sp, mass);
-        } else {
-            I = {{kScalarMax, 0, 0}, {0, kScalarMax, 0}, {0, 0, kScalarMax}};
-        }
-        if (has_com && !(r.has_inertia && r.has_inertia[l])) {   // shift_moment_of_inertia (moment_of_inertia.cpp:217-220): I + (d^T d) m, d = skew(com)
-            const m3 d = {{0, -com.z, com.y}, {com.z, 0, -com.x}, {-com.y, com.x, 0}};
-            const m3 dd = mul(transpose(d), d);
-            I = {I.r0 + dd.r0 * mass, I.r1 + dd.r1 * mass, I.r2 + dd.r2 * mass};
-        }
-        // inverse_matrix_symmetric, matrix3x3.hpp:190-218
-        float det = dot(I.r0, cross(I.r1, I.r2));
-        float di = 1.0f / det;
-        float a11 = I.r0.x, a12 = I.r0.y, a13 = I.r0.z, a22 = I.r1.y, a23 = I.r1.z, a33 = I.r2.z;
-        il.r0.x = di * (a22 * a33 - a23 * a23);
-        il.r0.y = di * (a13 * a23 - a12 * a33);
-        il.r0.z = di * (a12 * a23 - a13 * a22);
-        il.r1.x = il.r0.y;
-        il.r1.y = di * (a11 * a33 - a13 * a13);
-        il.r1.z = di * (a12 * a13 - a11 * a23);
-        il.r2.x = il.r0.z;
-        il.r2.y = il.r1.z;
-        il.r2.z = di * (a11 * a22 - a12 * a12);
-        m3 basis = to_m3(orn);
-        iw = mul(mul(basis, il), transpose(basis));
+        il = local_inertia_inv((r.has_inertia && r.has_inertia[l]) ? r.inertia + 9 * l : nullptr, st, sp, mass, com, has_com, meshes);
+        iw = world_inertia_inv(il, orn);
     }
     const bool moving = kind != EDYNHIP_KIND_STATIC;
     f3 lv = moving ? mk3(r.linvel[3 * l], r.linvel[3 * l + 1], r.linvel[3 * l + 2]) : mk3(0, 0, 0);
@@ -116,45 +63,8 @@ __global__ void k_init_bodies(uint32_t first, uint32_t n, RawBodies r, Bodies b,
     b.group[i] = r.group ? r.group[l] : ~0ull;
     b.mask[i] = r.mask ? r.mask[l] : ~0ull;
     b.island[i] = i;
-    // shape_aabb (aabb_util.cpp:11-70)
-    f3 mn = pos, mx = pos;
-    if (st == dc::SHAPE_BOX) {
-        const m3 basis = to_m3(orn);
-        const f3 h = from4(sp);
-        float lo[3] = {pos.x, pos.y, pos.z}, hi[3] = {pos.x, pos.y, pos.z};
-        const f3 rws[3] = {basis.r0, basis.r1, basis.r2};
-        for (int rr = 0; rr < 3; ++rr)
-            for (int cc = 0; cc < 3; ++cc) {
-                float e = comp(rws[rr], cc) * -comp(h, cc);
-                float f = -e;
-                if (e < f) { lo[rr] += e; hi[rr] += f; } else { lo[rr] += f; hi[rr] += e; }
-            }
-        mn = mk3(lo[0], lo[1], lo[2]); mx = mk3(hi[0], hi[1], hi[2]);
-    } else if (st == dc::SHAPE_SPHERE) {
-        mn = mk3(pos.x - sp.x, pos.y - sp.x, pos.z - sp.x); mx = mk3(pos.x + sp.x, pos.y + sp.x, pos.z + sp.x);
-    } else if (st == dc::SHAPE_CAPSULE) {   // aabb_util.cpp:81-88
-        const f3 v = rotate(orn, dc::axis_vector(sp.z)) * sp.y;
-        const f3 p0 = pos - v, p1 = pos + v;
-        mn = mk3(fminf(p0.x, p1.x) - sp.x, fminf(p0.y, p1.y) - sp.x, fminf(p0.z, p1.z) - sp.x);
-        mx = mk3(fmaxf(p0.x, p1.x) + sp.x, fmaxf(p0.y, p1.y) + sp.x, fmaxf(p0.z, p1.z) + sp.x);
-    } else if (st == dc::SHAPE_CYLINDER) {   // aabb_util.cpp:72-79
-        const box3 bb = dc::cylinder_aabb(dc::cyl_of(sp), pos, orn);
-        mn = bb.mn; mx = bb.mx;
-    } else if (st == dc::SHAPE_POLYHEDRON) {   // aabb_util.cpp:141-164,195-197
-        const box3 bb = dc::polyhedron_aabb(meshes, sp, pos, orn);
-        mn = bb.mn; mx = bb.mx;
-    } else if (st == dc::SHAPE_PLANE) {
-        const f3 nrm = from4(sp);
-        f3 umin = mk3(-1, -1, -1), umax = mk3(1, 1, 1);
-        if (eq(nrm, mk3(1, 0, 0))) umax = mk3(0, 1, 1);
-        else if (eq(nrm, mk3(-1, 0, 0))) umin = mk3(0, -1, -1);
-        else if (eq(nrm, mk3(0, 1, 0))) umax = mk3(1, 0, 1);
-        else if (eq(nrm, mk3(0, -1, 0))) umin = mk3(-1, 0, -1);
-        else if (eq(nrm, mk3(0, 0, 1))) umax = mk3(1, 1, 0);
-        else if (eq(nrm, mk3(0, 0, -1))) umin = mk3(-1, -1, 0);
-        const f3 pw = nrm * sp.w;
-        mn = umin * 99999.0f + pw; mx = umax * 99999.0f + pw;
-    }
+    f3 mn, mx;
+    shape_aabb(st, sp, pos, orn, meshes, mn, mx);
     b.amin[i] = to4(mn, 0); b.amax[i] = to4(mx, 0);
 }
 
@@ -208,7 +118,7 @@ __global__ void k_wake_marked(uint32_t n, Bodies b, uint32_t *wake, double *sinc
 }
 // Index lists handed to small kernels (bodies to wake, bodies to remove): one persistent device buffer that grows on demand
 // and is released with the context - no hipMalloc / hipFree per call, nothing to leak on an error path.
-static int index_scratch(edynhip_ctx *c, size_t count, uint32_t *&out) {
+int index_scratch(edynhip_ctx *c, size_t count, uint32_t *&out) {
     IndexScratch &s = c->idx_scratch;
     if (count > s.cap) {
         s.cap = 0;
@@ -218,6 +128,14 @@ static int index_scratch(edynhip_ctx *c, size_t count, uint32_t *&out) {
     }
     out = s.buf;
     return EDYNHIP_OK;
+}
+// The two halves of a wake-up for callers that mark more islands in between (body_edit.hip): sleep_action[label] = 1 for the islands of
+// the listed bodies (device list; the caller cleared sleep_action), and every dynamic body of a marked island awake, its timer restarted
+void mark_islands_of(edynhip_ctx *c, uint32_t n, const uint32_t *list_dev) {
+    if (n) hipLaunchKernelGGL(k_mark_touching, dim3(blocks(n, 128)), dim3(128), 0, c->stream, n, list_dev, c->b, c->sleep_action);
+}
+void wake_marked_islands(edynhip_ctx *c) {
+    if (c->b.n) hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since);
 }
 // wake the islands of the listed bodies (wake_up_island, island_manager.cpp:541-571)
 int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies) {
@@ -235,7 +153,7 @@ int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies) {
 }
 
 // broadphase participants from the host mirror of (kind, shape): [shaped non-procedural ..., shaped procedural ...]
-static int rebuild_broadphase_lists(edynhip_ctx *c) {
+int rebuild_broadphase_lists(edynhip_ctx *c) {
     uint32_t num_np = 0;
     const std::vector<uint32_t> list = broadphase_participants(c->host_kind, c->host_shape, num_np);
     // only procedural shaped bodies own pairs; everybody else's count must read 0 in the scan
@@ -304,6 +222,8 @@ static int load_bodies(edynhip_ctx *c, uint32_t first, uint32_t n, const edynhip
             hipLaunchKernelGGL(k_init_bodies, dim3(blocks(n, 256)), dim3(256), 0, c->stream, first, n, r, c->b,
                                make_float3(c->cfg.gravity[0], c->cfg.gravity[1], c->cfg.gravity[2]), c->meshes);
         c->host_kind.resize(first); c->host_shape.resize(first);
+        c->host_removed.resize(first, 0); c->host_removed.resize((size_t)first + n, 0); c->host_nosleep.resize(first, 0);   // (an upload holds no tombstones)
+        for (uint32_t i = 0; i < n; ++i) c->host_nosleep.push_back(in->sleeping_disabled && in->sleeping_disabled[i] ? 1 : 0);
         c->host_kind.insert(c->host_kind.end(), in->kind, in->kind + n);
         c->host_shape.insert(c->host_shape.end(), in->shape_type, in->shape_type + n);
         EH_TRY(rebuild_broadphase_lists(c));
@@ -332,7 +252,7 @@ static int load_bodies(edynhip_ctx *c, uint32_t first, uint32_t n, const edynhip
 // Host joint list -> device arrays: deterministic edge colouring over the live joints in caller-index order (ctx_rules.hpp
 // colour_joints), colour-sorted upload, applied impulses and hinge angles carried along.
 // fetch = first read the current impulses / angles back from the device (the joints were stepped since the last rebuild).
-static int rebuild_joints(edynhip_ctx *c, bool fetch) {
+int rebuild_joints(edynhip_ctx *c, bool fetch) {
     Joints &j = c->j;
     invalidate_topology_changed(c);
     hipStream_t s = c->stream;
@@ -544,7 +464,7 @@ int edynhip_remove_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices) {
     hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return set_error(c, EDYNHIP_ERR_HIP, "edynhip_remove_bodies", e);
-    for (uint32_t k = 0; k < n; ++k) { c->host_kind[indices[k]] = EDYNHIP_KIND_STATIC; c->host_shape[indices[k]] = EDYNHIP_SHAPE_NONE; }
+    for (uint32_t k = 0; k < n; ++k) { c->host_kind[indices[k]] = EDYNHIP_KIND_STATIC; c->host_shape[indices[k]] = EDYNHIP_SHAPE_NONE; c->host_removed[indices[k]] = 1; }
     std::vector<uint32_t> &excl = c->exclusions.host;
     if (!excl.empty())
         for (uint32_t k = 0; k < n; ++k) std::fill(excl.begin() + (size_t)indices[k] * 16, excl.begin() + (size_t)indices[k] * 16 + 16, 0xFFFFFFFFu);

@@ -114,6 +114,15 @@ __device__ __forceinline__ const float *mix_lookup(const Bodies &b, uint32_t bod
     const int32_t e = b.mix_lut[(size_t)c0 * b.mix_K + c1];
     return e < 0 ? nullptr : b.mix_vals + 6 * (size_t)e;
 }
+// Friction and restitution of a contact point created now between body0 and body1 (assign_material_properties,
+// collision_util.cpp:293-299): the mix table's entry for the pair, else the mixing rules. The one routine both the narrowphase and a
+// friction edit (body_edit.hip k_edit_friction) take a point's coefficients from; returns whether the table combined the pair.
+__device__ __forceinline__ bool mix_point_material(const Bodies &b, uint32_t body0, uint32_t body1, float2 mat0, float2 mat1, float &friction, float &restitution) {
+    friction = sqrtf(mat0.x * mat1.x);             // material_mixing.hpp:16-18
+    restitution = fminf(mat0.y, mat1.y);           // :12-14
+    if (const float *e = mix_lookup(b, body0, body1)) { restitution = e[0]; friction = e[1]; return true; }
+    return false;
+}
 
 // Contact events (EDYNHIP_FLAG_CONTACT_EVENTS; edynhip.h edynhip_contact_event has the same layout).
 struct ContactEvent { uint32_t type, step, bodyA, bodyB; uint64_t pid; };
@@ -516,6 +525,7 @@ struct edynhip_ctx {
     uint32_t *excl = nullptr;      // collision exclusion lists [max_bodies][16], ~0u-terminated (read by the broadphase); allocated by the first upload of an exclusion
     eh::ExclusionLists exclusions; // their host mirror
     std::vector<int32_t> host_kind, host_shape;   // per body, for rebuilding the broadphase lists when bodies are appended
+    std::vector<uint8_t> host_removed, host_nosleep;   // per body: the index is a tombstone (edynhip_remove_bodies); sleeping_disabled_tag (edynhip_edit_bodies keeps num_sleepable by it)
     // raycast queries (raycast.hip): a query tree of their own, rebuilt at the first raycast after state_epoch moved on
     uint64_t state_epoch = 1;      // bumped by everything that moves bodies or changes the set of bodies / their shapes
     eh::RayTree *ray = nullptr;
@@ -555,6 +565,10 @@ namespace eh {
 //   graph_changed(woke = false)     x                                                                               set_sleep_timers, a partial run_stages
 //   woke                                           x                                                                wake_all, wake_islands_of
 //   step_failed                     x                                 x (and full_step)                             a stage of run_stages failed
+//   bodies_edited(reshaped)                        x                                      x            x            edynhip_edit_bodies: SHAPE or KIND named
+//   bodies_edited(rekinded)         x              x                                      x            x          x  ... KIND named: who is procedural changed
+//   bodies_edited(dropped)          x              x                  x                                             ... manifolds left the array
+//   bodies_edited(none of them)                                                                                     ... MASS, INERTIA, MATERIAL: nothing
 // Differences between look-alikes that are kept as they are: edynhip_remove_bodies does not bump topology_epoch itself (only through the
 // joints it removes) where load_bodies does, and load_bodies bumps it before it has validated its arguments; edynhip_set_sleep_timers
 // forces the relabel without touching all_asleep where edynhip_set_asleep does both; edynhip_set_center_of_mass wakes nobody where
@@ -567,6 +581,11 @@ inline void invalidate_contact_state_replaced(edynhip_ctx *c) { c->force_islands
 inline void invalidate_topology_changed(edynhip_ctx *c) { ++c->topology_epoch; }
 inline void invalidate_graph_changed(edynhip_ctx *c, bool woke) { c->force_islands = true; if (woke) c->all_asleep = false; }
 inline void invalidate_step_failed(edynhip_ctx *c) { c->clears_primed = false; c->full_step = false; c->force_islands = true; }
+inline void invalidate_bodies_edited(edynhip_ctx *c, bool reshaped, bool rekinded, bool dropped) {
+    if (reshaped || rekinded) { c->all_asleep = false; c->bvh.lists_dirty = true; ++c->state_epoch; }
+    if (rekinded) { c->force_islands = true; ++c->topology_epoch; }
+    if (dropped) { c->force_islands = true; c->all_asleep = false; c->clears_primed = false; }
+}
 
 // stage entry points (each .hip file implements its own)
 int broadphase(edynhip_ctx *c);
@@ -594,6 +613,14 @@ int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies);   // c
 // capi_scene.hip: what the step entry points (capi.hip) and the state edits (capi_readback.hip) bring up to date first
 EH_LOCAL int flush_joint_redefs(edynhip_ctx *c);   // joints redefined since the device arrays were built
 EH_LOCAL int flush_exclusions(edynhip_ctx *c);     // exclusion rows edited since the last upload
+// capi_scene.hip, shared with body_edit.hip: the growing index buffer, the broadphase's participant lists from host_kind / host_shape, and the
+// joints' device arrays from the host list
+EH_LOCAL int index_scratch(edynhip_ctx *c, size_t count, uint32_t *&out);
+EH_LOCAL int rebuild_broadphase_lists(edynhip_ctx *c);
+EH_LOCAL int rebuild_joints(edynhip_ctx *c, bool fetch);
+EH_LOCAL void mark_islands_of(edynhip_ctx *c, uint32_t n, const uint32_t *list_dev);
+EH_LOCAL void wake_marked_islands(edynhip_ctx *c);
+EH_LOCAL int mesh_bind_body(edynhip_ctx *c, uint32_t body, uint32_t mesh_id);   // mesh.hip: mesh_bind_bodies for one body of a running world
 EH_LOCAL int enqueue_event_prefetch(edynhip_ctx *c);   // capi_readback.hip: this call's event count and list -> the pinned prefetch buffer
 // sort helpers (sort.hip)
 size_t sort_temp_bytes(uint32_t max_items);

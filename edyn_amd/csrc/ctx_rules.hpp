@@ -152,4 +152,52 @@ inline std::vector<uint32_t> broadphase_participants(const std::vector<int32_t> 
     return np_list;
 }
 
+// ------------------------------------------------------------------------------------------------ body edits
+// What edynhip_edit_bodies refuses, decided before anything on the device changes. removed[b] != 0: index b is a tombstone
+// (edynhip_remove_bodies); num_meshes: the convex meshes the context holds. Returns EDYNHIP_OK or the status of the first fault found,
+// with *why (a literal) saying which. The faults, in the order they are looked for: a mask beyond the five groups or a missing array
+// (INVALID); an index out of range, a tombstone, an index listed twice (INVALID); INERTIA to be derived (has_inertia 0) without MASS
+// (INVALID); a shape type outside box .. polyhedron (UNSUPPORTED); a polyhedron whose shape_param[0] is no mesh id (INVALID); a kind
+// that is none (INVALID); a body made dynamic without MASS and INERTIA in the same call (INVALID).
+constexpr uint32_t kEditGroups = EDYNHIP_EDIT_MASS | EDYNHIP_EDIT_INERTIA | EDYNHIP_EDIT_MATERIAL | EDYNHIP_EDIT_SHAPE | EDYNHIP_EDIT_KIND;
+inline int validate_body_edit(uint32_t n, const uint32_t *indices, const edynhip_bodies *v, uint32_t fields, uint32_t num_bodies,
+                              const std::vector<uint8_t> &removed, uint32_t num_meshes, const char **why) {
+    auto fail = [&](int code, const char *msg) { if (why) *why = msg; return code; };
+    if (fields & ~kEditGroups) return fail(EDYNHIP_ERR_INVALID, "unknown field group");
+    if (n == 0) return EDYNHIP_OK;
+    if (!indices || !v) return fail(EDYNHIP_ERR_INVALID, "missing indices or values");
+    if (((fields & EDYNHIP_EDIT_MASS) && !v->mass) || ((fields & EDYNHIP_EDIT_MATERIAL) && (!v->friction || !v->restitution)) ||
+        ((fields & EDYNHIP_EDIT_SHAPE) && (!v->shape_type || !v->shape_param)) || ((fields & EDYNHIP_EDIT_KIND) && !v->kind))
+        return fail(EDYNHIP_ERR_INVALID, "missing array of a named group");
+    for (uint32_t k = 0; k < n; ++k) {
+        if (indices[k] >= num_bodies) return fail(EDYNHIP_ERR_INVALID, "index out of range");
+        if (indices[k] < removed.size() && removed[indices[k]]) return fail(EDYNHIP_ERR_INVALID, "index of a removed body");
+    }
+    {   // (sorted copy: the cost follows the edit list, not the world)
+        std::vector<uint32_t> sorted(indices, indices + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(EDYNHIP_ERR_INVALID, "index listed twice");
+    }
+    if (fields & EDYNHIP_EDIT_INERTIA)
+        for (uint32_t k = 0; k < n; ++k) {
+            const bool given = v->has_inertia && v->has_inertia[k];
+            if (given && !v->inertia) return fail(EDYNHIP_ERR_INVALID, "has_inertia set without an inertia array");
+            if (!given && !(fields & EDYNHIP_EDIT_MASS)) return fail(EDYNHIP_ERR_INVALID, "an inertia derived from the shape needs MASS in the same call");
+        }
+    if (fields & EDYNHIP_EDIT_SHAPE)
+        for (uint32_t k = 0; k < n; ++k) {
+            if (v->shape_type[k] < EDYNHIP_SHAPE_BOX || v->shape_type[k] > EDYNHIP_SHAPE_POLYHEDRON) return fail(EDYNHIP_ERR_UNSUPPORTED, "shape type outside box .. polyhedron");
+            const float id = v->shape_param[4 * (size_t)k];
+            if (v->shape_type[k] == EDYNHIP_SHAPE_POLYHEDRON && (!(id >= 0) || id != std::floor(id) || id >= (float)num_meshes))
+                return fail(EDYNHIP_ERR_INVALID, "polyhedron: shape_param[0] is not the id of a mesh");
+        }
+    if (fields & EDYNHIP_EDIT_KIND)
+        for (uint32_t k = 0; k < n; ++k) {
+            if (v->kind[k] < EDYNHIP_KIND_DYNAMIC || v->kind[k] > EDYNHIP_KIND_STATIC) return fail(EDYNHIP_ERR_INVALID, "kind is none of dynamic, kinematic, static");
+            if (v->kind[k] == EDYNHIP_KIND_DYNAMIC && (fields & (EDYNHIP_EDIT_MASS | EDYNHIP_EDIT_INERTIA)) != (EDYNHIP_EDIT_MASS | EDYNHIP_EDIT_INERTIA))
+                return fail(EDYNHIP_ERR_INVALID, "a body made dynamic needs MASS and INERTIA in the same call");
+        }
+    return EDYNHIP_OK;
+}
+
 }  // namespace eh

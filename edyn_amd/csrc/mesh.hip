@@ -225,6 +225,24 @@ static int upload_meshes(edynhip_ctx *c, edynhip_ctx::HostMeshes &t) {
     return EDYNHIP_OK;
 }
 
+// What the first polyhedron of a context brings into existence, and room for every slice handed out so far
+static int ensure_poly_storage(edynhip_ctx *c) {
+    if (!c->poly_work) {   // the polyhedron narrowphase's binning scratch (narrowphase.hip PolyBins), with the first polyhedron of the context
+        const size_t cap = c->m[0].cap, words = 3 * 1024 + 1 + 4 * cap;   // bins, total, keys, list, two hint arrays
+        EH_HIP(c, hipMalloc((void **)&c->poly_work, words * sizeof(uint32_t)));
+        EH_HIP(c, hipMemsetAsync(c->poly_work, 0, (3 * 1024 + 1) * sizeof(uint32_t), c->stream));
+        EH_HIP(c, hipMemsetAsync(c->poly_work + 3 * 1024 + 1 + 2 * cap, 0, 2 * cap * sizeof(uint32_t), c->stream));   // no hints yet
+    }
+    if (c->rot_used > c->rot_cap) {   // contents are recomputed before every use: nothing to carry over
+        EH_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->rot) (void)hipFree(c->rot);
+        c->rot = nullptr;
+        c->rot_cap = std::max<size_t>(c->rot_used, c->rot_cap * 2);
+        EH_HIP(c, hipMalloc((void **)&c->rot, c->rot_cap * sizeof(float4)));
+    }
+    return EDYNHIP_OK;
+}
+
 // Called by load_bodies (capi.hip) before the bodies are initialised: checks the mesh ids of the polyhedra among bodies
 // [first, first + n) and gives each its slice of the rotated-mesh buffer.
 int mesh_bind_bodies(edynhip_ctx *c, uint32_t first, uint32_t n, const int32_t *shape_type, const float *shape_param) {
@@ -245,20 +263,23 @@ int mesh_bind_bodies(edynhip_ctx *c, uint32_t first, uint32_t n, const int32_t *
     }
     if (!any && !c->has_polyhedron) return EDYNHIP_OK;
     c->has_polyhedron = c->has_polyhedron || any;
-    if (!c->poly_work) {   // the polyhedron narrowphase's binning scratch (narrowphase.hip PolyBins), with the first polyhedron of the context
-        const size_t cap = c->m[0].cap, words = 3 * 1024 + 1 + 4 * cap;   // bins, total, keys, list, two hint arrays
-        EH_HIP(c, hipMalloc((void **)&c->poly_work, words * sizeof(uint32_t)));
-        EH_HIP(c, hipMemsetAsync(c->poly_work, 0, (3 * 1024 + 1) * sizeof(uint32_t), c->stream));
-        EH_HIP(c, hipMemsetAsync(c->poly_work + 3 * 1024 + 1 + 2 * cap, 0, 2 * cap * sizeof(uint32_t), c->stream));   // no hints yet
-    }
-    if (c->rot_used > c->rot_cap) {   // contents are recomputed before every use: nothing to carry over
-        EH_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->rot) (void)hipFree(c->rot);
-        c->rot = nullptr;
-        c->rot_cap = std::max<size_t>(c->rot_used, c->rot_cap * 2);
-        EH_HIP(c, hipMalloc((void **)&c->rot, c->rot_cap * sizeof(float4)));
-    }
+    EH_TRY(ensure_poly_storage(c));
     EH_HIP(c, hipMemcpyAsync(c->rot_off + first, c->host_rot_off.data() + first, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    EH_HIP(c, hipStreamSynchronize(c->stream));
+    c->meshes.rot = c->rot;
+    c->meshes.rot_off = c->rot_off;
+    return EDYNHIP_OK;
+}
+
+// The same for one body of a running world (edynhip_edit_bodies, SHAPE): the body gets a slice of its own at the end of the buffer. A
+// slice it held before is not handed out again - it stays unused until the context goes. The caller has checked mesh_id.
+int mesh_bind_body(edynhip_ctx *c, uint32_t body, uint32_t mesh_id) {
+    c->host_rot_off.resize(std::max<size_t>(c->host_rot_off.size(), c->b.n), 0xFFFFFFFFu);
+    c->host_rot_off[body] = (uint32_t)c->rot_used;
+    c->rot_used += c->host_meshes.desc[mesh_id].rot_size;
+    c->has_polyhedron = true;
+    EH_TRY(ensure_poly_storage(c));
+    EH_HIP(c, hipMemcpyAsync(c->rot_off + body, c->host_rot_off.data() + body, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     EH_HIP(c, hipStreamSynchronize(c->stream));
     c->meshes.rot = c->rot;
     c->meshes.rot_off = c->rot_off;

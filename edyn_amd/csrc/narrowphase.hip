@@ -476,9 +476,8 @@ DI void np_merge_lane(const uint32_t m, const Manifolds &mf, const Bodies &b, fl
         }
         int n_out = 0;
         if (create) {
-            float friction = sqrtf(A.friction * B.friction);             // material_mixing.hpp:16-18
-            float restitution = fminf(A.restitution, B.restitution);     // :12-14
-            if (const float *e = mix_lookup(b, ia, ib)) { restitution = e[0]; friction = e[1]; }   // assign_material_properties, collision_util.cpp:293-299
+            float friction, restitution;
+            mix_point_material(b, ia, ib, make_float2(A.friction, A.restitution), make_float2(B.friction, B.restitution), friction, restitution);
 #pragma unroll
             for (int i = kMaxPts - 1; i >= 0; --i) {
                 if ((create >> i) & 1u) {

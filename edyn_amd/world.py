@@ -256,6 +256,47 @@ class World:
         idx = np.ascontiguousarray(indices, np.uint32)
         self._check(self._L.edynhip_remove_bodies(self._h, len(idx), _ptr(idx)))
 
+    def edit_bodies(self, indices, mass=None, inertia=None, friction=None, restitution=None, shape_type=None, shape_param=None,
+                    kind=None, gravity=None):
+        """set_rigidbody_mass / _inertia / _friction, rigidbody_set_shape, rigidbody_set_kind on a running world, in place
+        (edynhip_edit_bodies). One entry per index; the groups edited follow from the arguments given: mass -> MASS; inertia ([n][9], a
+        row of NaN = derive it from shape and mass, which then must be given too) -> INERTIA; friction and / or restitution -> MATERIAL
+        (the one not given keeps the value last uploaded); shape_type with shape_param -> SHAPE; kind (with gravity, else the world's) ->
+        KIND, which needs mass and inertia for a body made dynamic."""
+        self._flush_defs()
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        n = len(idx)
+        a, fields = {}, 0
+        if mass is not None:
+            a["mass"] = np.ascontiguousarray(np.broadcast_to(np.asarray(mass, np.float32), (n,)))
+            fields |= _capi.EDIT_MASS
+        if inertia is not None:
+            I = np.ascontiguousarray(np.broadcast_to(np.asarray(inertia, np.float32).reshape(-1, 9), (n, 9)))
+            a["has_inertia"] = np.ascontiguousarray(~np.isnan(I).any(axis=1), np.uint8)
+            a["inertia"] = np.ascontiguousarray(np.nan_to_num(I))
+            fields |= _capi.EDIT_INERTIA
+        if friction is not None or restitution is not None:
+            if idx.size and idx.max() >= len(self._mat[0]):
+                raise EdynHipError(-1, "edit_bodies: body index out of range")
+            a["friction"] = np.ascontiguousarray(np.broadcast_to(np.asarray(self._mat[0][idx] if friction is None else friction, np.float32), (n,)))
+            a["restitution"] = np.ascontiguousarray(np.broadcast_to(np.asarray(self._mat[1][idx] if restitution is None else restitution, np.float32), (n,)))
+            fields |= _capi.EDIT_MATERIAL
+        if shape_type is not None:
+            a["shape_type"] = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_type, np.int32), (n,)))
+            a["shape_param"] = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_param, np.float32).reshape(-1, 4), (n, 4)))
+            fields |= _capi.EDIT_SHAPE
+        if kind is not None:
+            a["kind"] = np.ascontiguousarray(np.broadcast_to(np.asarray(kind, np.int32), (n,)))
+            if gravity is not None:
+                a["gravity"] = np.ascontiguousarray(np.broadcast_to(np.asarray(gravity, np.float32).reshape(-1, 3), (n, 3)))
+            fields |= _capi.EDIT_KIND
+        b = _capi.Bodies()
+        for f, _ in _capi.Bodies._fields_:
+            setattr(b, f, _ptr(a.get(f)))
+        self._check(self._L.edynhip_edit_bodies(self._h, n, _ptr(idx), C.byref(b), fields))
+        if fields & _capi.EDIT_MATERIAL:   # (after the call: a refused edit changes nothing)
+            self._mat[0][idx] = a["friction"]; self._mat[1][idx] = a["restitution"]
+
     def set_params(self, fixed_dt=None, velocity_iterations=None, position_iterations=None, gravity=None,
                    restitution_iterations=None, individual_restitution_iterations=None):
         """set_fixed_dt / set_solver_*_iterations / set_gravity on the running world: no contact state is lost."""
@@ -300,6 +341,7 @@ class World:
                 self._mesh_sig.append(sig[k])
         self._check(self._L.edynhip_set_bodies(self._h, n, C.byref(b)))
         self.n = n
+        self._mat = [keep["friction"].copy(), keep["restitution"].copy()]   # host copy of the materials (edit_bodies: the coefficient not given)
         self._upload_joints(joints)
         self._uploaded = (n, len(joints))
         self._dirty = False
@@ -313,6 +355,7 @@ class World:
         first = self.n
         self._check(self._L.edynhip_add_bodies(self._h, n, C.byref(b)))
         self.n += n
+        self._mat = [np.concatenate([m, keep[k]]) for m, k in zip(self._mat, ("friction", "restitution"))]
         return first
 
     def _flush_defs(self):

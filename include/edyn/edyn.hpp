@@ -257,8 +257,8 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
     // the world as it is to one context (edynhip.h "Edits of a RUNNING multi-device world"): bodies and constraints made after attach,
     // their definitions, exclude_collision, registry.destroy of either, edyn::refresh and settings changes keep every contact's warm
     // start, the joints' impulses and angles, sleep timers and the step count - the registry program computes what it computes on one
-    // device, bit for bit. What the single-device path also answers with a fresh upload (a shape, kind, mass or material edit, a
-    // convex mesh first seen after the bodies went up) still rebuilds the world from the registry.
+    // device, bit for bit. A shape, kind, mass, inertia or friction edit - applied in place on one device (rebuild_on_body_edit) - and a
+    // convex mesh first seen after the bodies went up still rebuild the world from the registry.
     std::vector<int> devices{};
     unsigned max_bodies{0};      // 0 = sized at the first upload (count + 25 % head-room)
     unsigned max_manifolds{0};
@@ -276,6 +276,11 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
     // EDYNHIP_FLAG_EXCLUSIVE_DEVICE: a promise that this stepper is the only user of its GPU while it steps - the resident-grid
     // solver kernels are then launched plainly instead of cooperatively (edynhip.h). Off = always safe.
     bool exclusive_device{false};
+    // set_rigidbody_mass / _inertia / _friction, rigidbody_set_shape and rigidbody_set_kind on a body that is already on the device are
+    // applied to the running context in place (edynhip.h edynhip_edit_bodies): no contact, joint impulse, sleep timer or contact entity of
+    // any other body is touched. true: the path from before that call existed - the next update re-creates the context from the
+    // registry and carries the contact state over (A/B runs; a world over several devices always takes it).
+    bool rebuild_on_body_edit{false};
 };
 
 /// Host time the shim itself spent around the device calls, accumulated over updates (edyn::get_shim_timings / reset_shim_timings):
@@ -284,6 +289,7 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
 struct shim_timings {
     double sync_removed{0}, upload{0}, step_call{0}, state_wait{0}, write_back{0}, contacts{0}, presentation{0}, total{0};
     uint64_t updates{0}, steps{0}, contact_events{0};   // contact_events: manifold / point creations and destructions carried into the registry
+    uint64_t context_rebuilds{0};   // times a running device context was destroyed and made again (capacity growth, rebuild_on_body_edit, a body edit that could not be applied in place)
 };
 
 class stepper_error : public std::runtime_error {
@@ -488,7 +494,8 @@ struct gpu_stepper {
     bool refresh_friction{false};  // set_rigidbody_friction: the carried contact points take the bodies' current materials (rigidbody.cpp:324-350)
     std::vector<std::pair<std::shared_ptr<convex_mesh>, uint32_t>> meshes;   // convex meshes the current device context holds, with their ids
     std::vector<uint32_t> reshaped;   // bodies whose shape / kind changed: their contacts are detected afresh by the re-created context
-    bool recreate{false};          // a body's mass / inertia / material was edited: the next upload re-creates the context (contacts, joints and sleep state are carried)
+    bool recreate{false};          // the next upload re-creates the context (contacts, joints and sleep state are carried): init_config::rebuild_on_body_edit, or an edit that cannot be applied in place
+    std::vector<std::pair<uint32_t, uint32_t>> body_edits;   // (body index, EDYNHIP_EDIT_* groups) edited since the last update: applied in place by flush_body_edits
     bool contacts_resync{false};   // the context was re-created (capacity growth): point ids changed, rebuild the contact entities
     bool snapshot_pending{false};                                   // asynchronous mode: a snapshot of the previous update is in flight
     shim_timings tm;                                                // host time per phase (edyn::get_shim_timings)
@@ -607,15 +614,16 @@ struct body_arrays {
 };
 // mesh_id(polyhedron_shape) -> the id of its mesh in the device context (created there on first sight)
 template <typename MeshId>
-inline void fill_body_arrays(entt::registry &registry, gpu_stepper &s, uint32_t first, uint32_t n, body_arrays &A, MeshId &&mesh_id) {
+inline void fill_body_arrays(entt::registry &registry, gpu_stepper &s, uint32_t first, uint32_t n, body_arrays &A, MeshId &&mesh_id, const uint32_t *list = nullptr) {   // list: the n body indices instead of the range
     auto &kind = A.kind; auto &stype = A.stype; auto &pos = A.pos; auto &orn = A.orn; auto &lv = A.lv; auto &av = A.av; auto &m = A.m; auto &I = A.I;
     auto &sp = A.sp; auto &fr = A.fr; auto &re = A.re; auto &g = A.g; auto &com = A.com; auto &xspin = A.xspin; auto &xroll = A.xroll; auto &xstiff = A.xstiff;
     auto &xdamp = A.xdamp; auto &hasI = A.hasI; auto &nosleep = A.nosleep; auto &mat_ids = A.mat_ids; auto &dead = A.dead; auto &grp = A.grp; auto &msk = A.msk;
     bool &any_com = A.any_com; bool &any_extras = A.any_extras; bool &any_ids = A.any_ids;
     for (uint32_t i = 0; i < n; ++i) {
-        const entt::entity e = s.bodies[first + i];
+        const uint32_t index = list ? list[i] : first + i;
+        const entt::entity e = s.bodies[index];
         if (e == entt::null) {   // destroyed before it was ever uploaded (or before a re-upload): a shapeless static placeholder
-            kind[i] = EDYNHIP_KIND_STATIC; stype[i] = EDYNHIP_SHAPE_NONE; orn[4 * i + 3] = 1.f; dead.push_back(first + i);
+            kind[i] = EDYNHIP_KIND_STATIC; stype[i] = EDYNHIP_SHAPE_NONE; orn[4 * i + 3] = 1.f; dead.push_back(index);
             continue;
         }
         kind[i] = registry.all_of<dynamic_tag>(e) ? EDYNHIP_KIND_DYNAMIC : registry.all_of<kinematic_tag>(e) ? EDYNHIP_KIND_KINEMATIC : EDYNHIP_KIND_STATIC;
@@ -749,7 +757,7 @@ inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     for (const auto &e : s.exclusions) check(s, edynhip_world_exclude_collision(s.world, e[0], e[1]));
     s.uploaded_bodies = total; s.uploaded_constraints = nj; s.exclusions_uploaded = s.exclusions.size();
     s.scene_dirty = false; s.state_dirty = false;
-    s.recreate = false; s.refresh_friction = false; s.reshaped.clear();   // (the new world was described with the current components)
+    s.recreate = false; s.refresh_friction = false; s.reshaped.clear(); s.body_edits.clear();   // (the new world was described with the current components)
     s.params_dirty = false;                                               // (... and created with the current settings)
 }
 // upload_scene's append path on a multi-device world: bodies, constraints, definitions and exclusions made since the last upload go to
@@ -822,6 +830,18 @@ inline void flush_materials(entt::registry &registry, gpu_stepper &s) {
     s.material_dirty.clear();
 }
 
+// The id of a polyhedron's mesh in the device context: the mesh goes up once per context, on first sight, however many bodies share it
+inline uint32_t context_mesh_id(gpu_stepper &s, const polyhedron_shape &ph, int *rc) {
+    for (auto &known : s.meshes) if (known.first == ph.mesh) return known.second;
+    uint32_t id = ~0u;
+    const convex_mesh &cm = *ph.mesh;
+    std::vector<float> mv(3 * cm.vertices.size());
+    for (size_t k = 0; k < cm.vertices.size(); ++k) { mv[3 * k] = cm.vertices[k].x; mv[3 * k + 1] = cm.vertices[k].y; mv[3 * k + 2] = cm.vertices[k].z; }
+    *rc = edynhip_create_convex_mesh(s.ctx, (uint32_t)cm.vertices.size(), mv.data(), (uint32_t)cm.indices.size(), cm.indices.data(),
+                                     (uint32_t)cm.num_faces(), cm.faces.data(), cm.initialized ? EDYNHIP_MESH_INITIALIZED : 0u, &id);
+    if (*rc == EDYNHIP_OK) s.meshes.emplace_back(ph.mesh, id);
+    return id;
+}
 constexpr uint32_t prefetch_events_max = 8192;   // contact events that travel ahead of a step's state (sequential modes); more = read after the step
 inline void upload_scene(entt::registry &registry, gpu_stepper &s) {
     const uint32_t total = (uint32_t)s.bodies.size();
@@ -833,7 +853,9 @@ inline void upload_scene(entt::registry &registry, gpu_stepper &s) {
     bool regrown = false;
     if (!s.ctx || total > s.capacity || nj > s.joint_capacity || s.recreate) {
         s.recreate = false;
+        s.body_edits.clear();   // (the new context is described with the components the registry holds now)
         if (s.ctx) {
+            ++s.tm.context_rebuilds;
             uint32_t m = 0;
             check(s, edynhip_num_manifolds(s.ctx, &m));
             carried.resize(m);
@@ -905,17 +927,10 @@ inline void upload_scene(entt::registry &registry, gpu_stepper &s) {
     // Bodies created since the last upload are appended (edynhip_add_bodies): the running contact state of the others stays.
     const uint32_t first = s.uploaded_bodies, n = total - first;
     body_arrays A(n);
-    fill_body_arrays(registry, s, first, n, A, [&](const polyhedron_shape &ph) {   // the mesh goes up once per context, however many bodies share it
-        uint32_t id = ~0u;
-        for (auto &known : s.meshes) if (known.first == ph.mesh) id = known.second;
-        if (id == ~0u) {
-            const convex_mesh &cm = *ph.mesh;
-            std::vector<float> mv(3 * cm.vertices.size());
-            for (size_t k = 0; k < cm.vertices.size(); ++k) { mv[3 * k] = cm.vertices[k].x; mv[3 * k + 1] = cm.vertices[k].y; mv[3 * k + 2] = cm.vertices[k].z; }
-            check(s, edynhip_create_convex_mesh(s.ctx, (uint32_t)cm.vertices.size(), mv.data(), (uint32_t)cm.indices.size(), cm.indices.data(),
-                                                (uint32_t)cm.num_faces(), cm.faces.data(), cm.initialized ? EDYNHIP_MESH_INITIALIZED : 0u, &id));
-            s.meshes.emplace_back(ph.mesh, id);
-        }
+    fill_body_arrays(registry, s, first, n, A, [&](const polyhedron_shape &ph) {
+        int rc = EDYNHIP_OK;
+        const uint32_t id = context_mesh_id(s, ph, &rc);
+        check(s, rc);
         return id;
     });
     const edynhip_bodies b = A.view();
@@ -981,6 +996,73 @@ inline void upload_scene(entt::registry &registry, gpu_stepper &s) {
     }
     s.scene_dirty = false;
     if (first == 0) s.state_dirty = false;
+}
+
+// set_rigidbody_mass / _inertia / _friction, rigidbody_set_shape, rigidbody_set_kind on bodies the context already holds: one
+// edynhip_edit_bodies call per set of groups, with the values the registry holds now. The manifolds a SHAPE or KIND edit drops are
+// reported as events behind the last step call's: the contact entities of those pairs go, every other entity stays what it is. A mesh the
+// context cannot take, or a body left without a shape, sends the edits down the old road: a context made again from the registry.
+inline void apply_contact_events(entt::registry &registry, gpu_stepper &s, std::vector<edynhip_contact_event> &ev, int rc);
+inline void flush_body_edits(entt::registry &registry, gpu_stepper &s) {
+    if (s.body_edits.empty()) return;
+    std::vector<std::pair<uint32_t, uint32_t>> edits;
+    edits.swap(s.body_edits);
+    if (!s.ctx) return;
+    constexpr uint32_t drops = EDYNHIP_EDIT_SHAPE | EDYNHIP_EDIT_KIND;
+    std::vector<std::pair<uint32_t, uint32_t>> todo;   // (groups, body), sorted: one call per set of groups
+    bool any_drop = false;
+    for (auto &e : edits) {
+        if (e.first >= s.uploaded_bodies || s.bodies[e.first] == entt::null) continue;
+        const entt::entity entity = s.bodies[e.first];
+        uint32_t g = e.second;
+        if ((g & EDYNHIP_EDIT_KIND) && registry.all_of<dynamic_tag>(entity)) g |= EDYNHIP_EDIT_MASS | EDYNHIP_EDIT_INERTIA;   // a body made dynamic takes both with it
+        // A body made without rigidbody_def::inertia carries no inertia component: the device derives its inertia from shape and mass at
+        // every upload, so another mass or shape derives it again here (what a re-created context computes for the same registry)
+        if ((g & (EDYNHIP_EDIT_MASS | EDYNHIP_EDIT_SHAPE | EDYNHIP_EDIT_INERTIA)) && !registry.all_of<inertia>(entity)) g |= EDYNHIP_EDIT_MASS | EDYNHIP_EDIT_INERTIA;
+        any_drop = any_drop || (g & drops);
+        todo.emplace_back(g, e.first);
+    }
+    std::sort(todo.begin(), todo.end());
+    auto rebuild_instead = [&]() {
+        for (auto &t : todo) { if (t.first & drops) s.reshaped.push_back(t.second); if (t.first & EDYNHIP_EDIT_MATERIAL) s.refresh_friction = true; }
+        s.recreate = s.scene_dirty = true;
+        upload_scene(registry, s);
+    };
+    uint32_t seen = 0;
+    int rc_seen = EDYNHIP_OK;
+    const bool mirror = any_drop && s.cfg.materialize_contacts;
+    if (mirror) rc_seen = edynhip_get_contact_events(s.ctx, nullptr, 0, &seen);   // the events already carried into the registry
+    for (size_t at = 0; at < todo.size();) {
+        size_t end = at;
+        while (end < todo.size() && todo[end].first == todo[at].first) ++end;
+        const uint32_t g = todo[at].first, n = (uint32_t)(end - at);
+        std::vector<uint32_t> list(n);
+        for (uint32_t k = 0; k < n; ++k) list[k] = todo[at + k].second;
+        body_arrays A(n);
+        int mesh_rc = EDYNHIP_OK;
+        fill_body_arrays(registry, s, 0, n, A, [&](const polyhedron_shape &ph) {
+            int rc = EDYNHIP_OK;
+            const uint32_t id = (g & EDYNHIP_EDIT_SHAPE) ? context_mesh_id(s, ph, &rc) : 0u;
+            if (rc != EDYNHIP_OK) mesh_rc = rc;
+            return id;
+        }, list.data());
+        bool shapeless = false;
+        if (g & EDYNHIP_EDIT_SHAPE) for (uint32_t k = 0; k < n; ++k) shapeless = shapeless || A.stype[k] == EDYNHIP_SHAPE_NONE;
+        if (mesh_rc != EDYNHIP_OK || shapeless) { rebuild_instead(); return; }
+        const edynhip_bodies b = A.view();
+        check(s, edynhip_edit_bodies(s.ctx, n, list.data(), &b, g));
+        at = end;
+    }
+    if (mirror) {
+        uint32_t n = 0;
+        int rc = edynhip_get_contact_events(s.ctx, nullptr, 0, &n);
+        std::vector<edynhip_contact_event> ev(n);
+        if (rc == EDYNHIP_OK && n) rc = edynhip_get_contact_events(s.ctx, ev.data(), n, &n);
+        if (rc != EDYNHIP_OK || rc_seen != EDYNHIP_OK || seen > n) { s.contacts_resync = true; return; }   // (a list that overflowed: the entities are rebuilt from the manifolds)
+        ev.erase(ev.begin(), ev.begin() + seen);
+        phase_timer t(s.tm.contacts);
+        apply_contact_events(registry, s, ev, EDYNHIP_OK);
+    }
 }
 
 inline void upload_state(entt::registry &registry, gpu_stepper &s) {
@@ -1359,7 +1441,7 @@ inline void run_steps(entt::registry &registry, gpu_stepper &s, unsigned steps, 
 }
 inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsigned steps, bool timed, double first_time, double step_dt) {
     const bool async = s.cfg.execution_mode == execution_mode::asynchronous;
-    if (async && s.records_pending && (s.state_dirty || s.scene_dirty || steps == 0 || s.pre_step || s.post_step)) {
+    if (async && s.records_pending && (s.state_dirty || s.scene_dirty || !s.body_edits.empty() || steps == 0 || s.pre_step || s.post_step)) {
         // execution_mode::asynchronous, the cases that cannot overlap: user edits pending (the snapshot is superseded by the device's
         // current state + the edits), a scene change (the context may be re-created), no step to overlap with
         if (s.state_dirty) {
@@ -1413,6 +1495,7 @@ inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsign
         phase_timer t(s.tm.upload);
         if (s.scene_dirty) upload_scene(registry, s);
         if (!s.material_dirty.empty()) flush_materials(registry, s);
+        if (!s.body_edits.empty()) flush_body_edits(registry, s);
         if (s.state_dirty) upload_state(registry, s);   // also after an append: edits made in the same frame are not lost
         apply_params(s);
     }
@@ -2398,26 +2481,44 @@ inline void set_kinematic_orientation(entt::registry &registry, entt::entity ent
     cur.x = orn.x; cur.y = orn.y; cur.z = orn.z; cur.w = orn.w;
     registry.ctx().get<detail::gpu_stepper>().state_dirty = true;
 }
+namespace detail {
+// An edit of a body's mass, inertia, material, shape or kind (EDYNHIP_EDIT_* groups). A body the context already holds is edited in
+// place at the next update (flush_body_edits); one that has not gone up yet takes its components with it. The road from before
+// edynhip_edit_bodies - the next upload re-creates the context - is taken with init_config::rebuild_on_body_edit, on a world over
+// several devices, and where the edit has no in-place form (a body left without a shape).
+inline void record_body_edit(entt::registry &registry, entt::entity entity, uint32_t groups, bool in_place_form = true) {
+    auto &s = registry.ctx().get<gpu_stepper>();
+    const body_index *bi = registry.try_get<body_index>(entity);
+    if (s.cfg.rebuild_on_body_edit || s.multi() || !in_place_form) {
+        s.recreate = s.scene_dirty = true;
+        if (groups & EDYNHIP_EDIT_MATERIAL) s.refresh_friction = true;
+        if ((groups & (EDYNHIP_EDIT_SHAPE | EDYNHIP_EDIT_KIND)) && bi) s.reshaped.push_back(bi->value);
+        return;
+    }
+    if (!bi || !s.ctx || bi->value >= s.uploaded_bodies) return;
+    for (auto &e : s.body_edits) if (e.first == bi->value) { e.second |= groups; return; }
+    s.body_edits.emplace_back(bi->value, groups);
+}
+}  // namespace detail
 /// rigidbody.cpp:301-352
 inline void set_rigidbody_mass(entt::registry &registry, entt::entity entity, scalar m) {
     registry.get<mass>(entity).s = m; registry.get<mass_inv>(entity).s = scalar(1) / m;
-    auto &s = registry.ctx().get<detail::gpu_stepper>(); s.recreate = s.scene_dirty = true;
+    detail::record_body_edit(registry, entity, EDYNHIP_EDIT_MASS);
 }
 inline void set_rigidbody_inertia(entt::registry &registry, entt::entity entity, const matrix3x3 &I) {
     registry.emplace_or_replace<inertia>(entity, inertia{I});
-    auto &s = registry.ctx().get<detail::gpu_stepper>(); s.recreate = s.scene_dirty = true;
+    detail::record_body_edit(registry, entity, EDYNHIP_EDIT_INERTIA);
 }
-inline void set_rigidbody_friction(entt::registry &registry, entt::entity entity, scalar friction) {   // (existing contact points take the new value with the re-created context)
+inline void set_rigidbody_friction(entt::registry &registry, entt::entity entity, scalar friction) {   // (the body's living contact points take the new value with the next update)
     registry.get<material>(entity).friction = friction;
-    auto &s = registry.ctx().get<detail::gpu_stepper>(); s.recreate = s.scene_dirty = s.refresh_friction = true;
+    detail::record_body_edit(registry, entity, EDYNHIP_EDIT_MATERIAL);
 }
-/// util/rigidbody.hpp:235-257 (rigidbody.cpp:417-515): another shape / no shape, another kind - through a re-created context like the edits above
+/// util/rigidbody.hpp:235-257 (rigidbody.cpp:417-515): another shape / no shape, another kind - in place like the edits above (no shape: a re-created context)
 inline bool rigidbody_has_shape(entt::registry &registry, entt::entity entity) { return registry.any_of<box_shape, sphere_shape, plane_shape, capsule_shape, cylinder_shape, polyhedron_shape>(entity); }
 inline void rigidbody_set_shape(entt::registry &registry, entt::entity entity, std::optional<shapes_variant_t> shape_opt) {
     registry.remove<box_shape>(entity); registry.remove<sphere_shape>(entity); registry.remove<plane_shape>(entity); registry.remove<capsule_shape>(entity); registry.remove<cylinder_shape>(entity); registry.remove<polyhedron_shape>(entity);
     if (shape_opt) std::visit([&](auto &&sh) { registry.emplace<std::decay_t<decltype(sh)>>(entity, sh); }, *shape_opt);
-    auto &s = registry.ctx().get<detail::gpu_stepper>(); s.recreate = s.scene_dirty = true;
-    if (auto *bi = registry.try_get<detail::body_index>(entity)) s.reshaped.push_back(bi->value);
+    detail::record_body_edit(registry, entity, EDYNHIP_EDIT_SHAPE, shape_opt.has_value());
 }
 inline void rigidbody_set_kind(entt::registry &registry, entt::entity entity, rigidbody_kind kind) {
     registry.remove<dynamic_tag>(entity); registry.remove<procedural_tag>(entity); registry.remove<kinematic_tag>(entity); registry.remove<static_tag>(entity);
@@ -2434,8 +2535,7 @@ inline void rigidbody_set_kind(entt::registry &registry, entt::entity entity, ri
         if (auto *v = registry.try_get<linvel>(entity)) *v = linvel{};
         if (auto *w = registry.try_get<angvel>(entity)) *w = angvel{};
     }
-    auto &s = registry.ctx().get<detail::gpu_stepper>(); s.recreate = s.scene_dirty = true;
-    if (auto *bi = registry.try_get<detail::body_index>(entity)) s.reshaped.push_back(bi->value);
+    detail::record_body_edit(registry, entity, EDYNHIP_EDIT_KIND);
 }
 /// rigidbody.cpp:409-415 -> island_manager wake_up_island
 inline void wake_up_entity(entt::registry &registry, entt::entity entity) {

@@ -225,6 +225,34 @@ int edynhip_set_joint_params(edynhip_ctx *ctx, uint32_t joint_index, const float
  * up. The body INDEX stays reserved (the slot reads back as a shapeless static body); every other index, manifold, warm-start
  * impulse and sleep timer is untouched. */
 int edynhip_remove_bodies(edynhip_ctx *ctx, uint32_t n, const uint32_t *body_indices);
+/* Bodies of a running world edited in place: set_rigidbody_mass / _inertia / _friction, rigidbody_set_shape, rigidbody_set_kind
+ * (src/edyn/util/rigidbody.cpp:300-362, :471-495, :579-606) without a fresh upload. values holds n entries parallel to indices; only the
+ * arrays of the groups named in `fields` are read. Each group changes what the reference call changes and nothing derived across groups:
+ *   MASS      mass: the inverse mass (:300-305).
+ *   INERTIA   inertia, has_inertia: the local inverse inertia as edynhip_set_bodies computes it, and the world inverse inertia from the
+ *             body's current orientation (:307-312). has_inertia[i] == 0 (or a NULL has_inertia): derived from the body's shape, the
+ *             mass given in this call and its centre-of-mass offset, as edynhip_set_bodies does - MASS must then be named too.
+ *             (Inverse mass and inertias are kept on the device for dynamic bodies only: on a body that is not dynamic after the call
+ *             both groups change nothing.)
+ *   MATERIAL  friction, restitution: the body's material. Every living contact point of the body's manifolds takes the friction a
+ *             point created now would get, except in a pair the mix table combines - those keep theirs (:314-362). Restitution
+ *             reaches new points only; a value above 0 turns the restitution solver on, as in edynhip_set_bodies.
+ *   SHAPE     shape_type (box .. polyhedron), shape_param: shape, flags and the AABB from the current pose; mass and inertia are left
+ *             alone; every manifold of the body is dropped (:471-495). A polyhedron gets a slice of the rotated-mesh buffer of its own;
+ *             a slice the body held before stays unused until the context is destroyed.
+ *   KIND      kind, gravity (NULL = the context's): to static or kinematic, inverse mass, inertias and gravity become 0, to static the
+ *             velocities too; to dynamic, MASS and INERTIA must be named in the same call. Every manifold of the body is dropped - the
+ *             reference keeps those against procedural partners (:591-605); see INTEGRATION.md section 3.
+ * A dropped manifold leaves the manifold array as if its pair had left the pair set: with EDYNHIP_FLAG_CONTACT_EVENTS a POINT_DESTROYED
+ * event per living point and a MANIFOLD_DESTROYED event are appended to the event list of the last step call; if the pair still overlaps
+ * the next step creates it anew. SHAPE and KIND wake the islands of the edited bodies, of every body that shared a dropped manifold with
+ * them and of every body that shares a joint with them, as edynhip_remove_bodies does; MASS, INERTIA and MATERIAL wake nobody and keep
+ * the candidate lists, the island labels and the solve schedule.
+ * Everything is checked before anything changes: EDYNHIP_ERR_INVALID for an index out of range, of a removed body or listed twice, for a
+ * polyhedron whose shape_param[0] is not a mesh id, for a missing array; EDYNHIP_ERR_UNSUPPORTED for a shape type outside box ..
+ * polyhedron and for a shard of a multi-device world. n == 0 is valid. */
+enum { EDYNHIP_EDIT_MASS = 1, EDYNHIP_EDIT_INERTIA = 2, EDYNHIP_EDIT_MATERIAL = 4, EDYNHIP_EDIT_SHAPE = 8, EDYNHIP_EDIT_KIND = 16 };
+int edynhip_edit_bodies(edynhip_ctx *ctx, uint32_t n, const uint32_t *indices, const edynhip_bodies *values, uint32_t fields);
 /* settings on a running world WITHOUT losing state: set_fixed_dt, set_solver_velocity/position_iterations, set_gravity
  * (src/edyn/edyn.cpp:203-207, src/edyn/config/solver_iteration_config.cpp:9-75, src/edyn/util/gravity_util.cpp:12-20 - like the
  * reference, set_gravity also replaces the gravity of every dynamic body). */
