@@ -146,7 +146,7 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_query_aabb_collect", "edynhip_query_release",
            "edynhip_world_raycast", "edynhip_world_raycast_device", "edynhip_world_query_aabb", "edynhip_world_query_aabb_device",
            "edynhip_world_get_contact_events", "edynhip_world_get_point_ids",
-           "edynhip_debug_paths", "edynhip_world_debug_paths",
+           "edynhip_debug_paths", "edynhip_world_debug_paths", "edynhip_debug_relabel_steps",
            # edits of a running multi-device world
            "edynhip_world_add_bodies", "edynhip_world_remove_bodies", "edynhip_world_add_joints", "edynhip_world_remove_joints",
            "edynhip_world_edit_joint", "edynhip_world_edit_exclusion", "edynhip_world_set_state", "edynhip_world_get_params",
@@ -205,6 +205,7 @@ def lib():
         L.edynhip_debug_collide.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p]
         L.edynhip_debug_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.edynhip_world_debug_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.edynhip_debug_relabel_steps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.edynhip_get_asleep.argtypes = [C.c_void_p, C.c_void_p]
         L.edynhip_wake_all.argtypes = [C.c_void_p]
         L.edynhip_wake_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]

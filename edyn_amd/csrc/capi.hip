@@ -401,6 +401,12 @@ int edynhip_debug_paths(edynhip_ctx *c, uint64_t *mask) {
     *mask = c->paths;
     return EDYNHIP_OK;
 }
+int edynhip_debug_relabel_steps(edynhip_ctx *c, uint64_t *full, uint64_t *incremental) {
+    if (!c || !full || !incremental) return EDYNHIP_ERR_INVALID;
+    *full = c->cc_full_steps;
+    *incremental = c->cc_incremental_steps;
+    return EDYNHIP_OK;
+}
 
 int edynhip_get_timings(edynhip_ctx *c, edynhip_timings *out) {
     if (!c || !out) return EDYNHIP_ERR_INVALID;

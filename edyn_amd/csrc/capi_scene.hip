@@ -108,13 +108,15 @@ __global__ void k_wake_partners(uint32_t M, Manifolds mf, Bodies b, uint32_t *wa
     if (ra && (b.flags[bb] & BF_KIND_MASK) == EDYNHIP_KIND_DYNAMIC) wake[b.island[bb]] = 1u;
     if (rb && (b.flags[a] & BF_KIND_MASK) == EDYNHIP_KIND_DYNAMIC) wake[b.island[a]] = 1u;
 }
-__global__ void k_wake_marked(uint32_t n, Bodies b, uint32_t *wake, double *since) {
+// restart: the island's sleep timer starts again as well (an edit of the body itself). wake_up_island (util/island_util.cpp:61-66) alone only takes
+// the sleeping tags off: the timer of an awake island that loses a joint or a body, or is woken by the caller, goes on running.
+__global__ void k_wake_marked(uint32_t n, Bodies b, uint32_t *wake, double *since, bool restart) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t fl = b.flags[i];
     if ((fl & BF_KIND_MASK) != EDYNHIP_KIND_DYNAMIC) return;
     const uint32_t l = b.island[i];
-    if (wake[l]) { b.flags[i] = fl & ~BF_ASLEEP; if (l == i) since[i] = -1.0; }
+    if (wake[l]) { b.flags[i] = fl & ~BF_ASLEEP; if (restart && l == i) since[i] = -1.0; }
 }
 // Index lists handed to small kernels (bodies to wake, bodies to remove): one persistent device buffer that grows on demand
 // and is released with the context - no hipMalloc / hipFree per call, nothing to leak on an error path.
@@ -135,7 +137,7 @@ void mark_islands_of(edynhip_ctx *c, uint32_t n, const uint32_t *list_dev) {
     if (n) hipLaunchKernelGGL(k_mark_touching, dim3(blocks(n, 128)), dim3(128), 0, c->stream, n, list_dev, c->b, c->sleep_action);
 }
 void wake_marked_islands(edynhip_ctx *c) {
-    if (c->b.n) hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since);
+    if (c->b.n) hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since, true);
 }
 // wake the islands of the listed bodies (wake_up_island, island_manager.cpp:541-571)
 int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies) {
@@ -145,7 +147,7 @@ int wake_islands_of(edynhip_ctx *c, const std::vector<uint32_t> &bodies) {
     EH_HIP(c, hipMemcpyAsync(list, bodies.data(), bodies.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     EH_HIP(c, hipMemsetAsync(c->sleep_action, 0, (size_t)c->b.n * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_mark_touching, dim3(blocks((uint32_t)bodies.size(), 128)), dim3(128), 0, c->stream, (uint32_t)bodies.size(), list, c->b, c->sleep_action);
-    hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since);
+    hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since, false);
     hipError_t e = hipStreamSynchronize(c->stream);   // the scratch list may be refilled by the next call
     invalidate_woke(c);
     if (e != hipSuccess) return set_error(c, EDYNHIP_ERR_HIP, "wake_islands_of", e);
@@ -242,6 +244,7 @@ static int load_bodies(edynhip_ctx *c, uint32_t first, uint32_t n, const edynhip
         (void)hipMemsetAsync(c->sleep_size, 0, (size_t)c->b.cap * sizeof(uint32_t), c->stream);
         (void)hipMemsetAsync(c->sleep_best, 0, (size_t)c->b.cap * sizeof(unsigned long long), c->stream);
         c->sleep_prev_n = 0;   // no islands of a previous step
+        c->sleep_prev_joints = 0;
         c->island_labels_valid = false;
         (void)hipStreamSynchronize(c->stream);
     }
@@ -439,6 +442,35 @@ int edynhip_add_bodies(edynhip_ctx *c, uint32_t n, const edynhip_bodies *in) {
     return load_bodies(c, c->b.n, n, in, "edynhip_add_bodies");
 }
 
+// The island entity outlives a node it loses, and with it its sleep timer (island_manager.cpp:74-97, 421-424). Here an island is named by its
+// lowest body index: where that body was removed, the name and the timer kept under it move to the lowest index that is left, so that the
+// next relabel finds last step's island under a body that still exists - whole (the timer goes on) or split (k_cc_flatten restarts it).
+// On the host: a removal synchronises anyway, and only worlds with island sleeping pay the two copies.
+static int rename_islands_of_removed_roots(edynhip_ctx *c, const std::vector<uint8_t> &gone) {
+    const uint32_t n = c->b.n;
+    if (!c->sleeping || !c->island_labels_valid || n == 0) return EDYNHIP_OK;
+    std::vector<uint32_t> label(n);
+    std::vector<double> since(n);
+    EH_HIP(c, hipMemcpyAsync(label.data(), c->b.island, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    EH_HIP(c, hipMemcpyAsync(since.data(), c->sleep_since, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    EH_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> heir(n, 0xFFFFFFFFu);
+    bool changed = false;
+    for (uint32_t i = 0; i < n; ++i) {   // ascending: the first member met is the lowest index left
+        const uint32_t l = label[i];
+        if (l >= n || l == i || !gone[l] || gone[i]) continue;
+        if (heir[l] == 0xFFFFFFFFu) { heir[l] = i; since[i] = since[l]; }
+        label[i] = heir[l];
+        changed = true;
+    }
+    for (uint32_t i = 0; i < n; ++i) if (gone[i] && since[i] >= 0.0) { since[i] = -1.0; changed = true; }
+    if (!changed) return EDYNHIP_OK;
+    EH_HIP(c, hipMemcpyAsync(c->b.island, label.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    EH_HIP(c, hipMemcpyAsync(c->sleep_since, since.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    EH_HIP(c, hipStreamSynchronize(c->stream));   // the vectors go out of scope
+    return EDYNHIP_OK;
+}
+
 int edynhip_remove_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices) {
     if (!c || (n && !indices)) return EDYNHIP_ERR_INVALID;
     if (n == 0) return EDYNHIP_OK;
@@ -461,9 +493,10 @@ int edynhip_remove_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices) {
     EH_HIP(c, hipMemsetAsync(c->sleep_action, 0, (size_t)c->b.n * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_mark_removed, dim3(blocks(n, 128)), dim3(128), 0, c->stream, n, list, c->b, c->sleep_action);
     if (c->num_manifolds) hipLaunchKernelGGL(k_wake_partners, dim3(blocks(c->num_manifolds, 256)), dim3(256), 0, c->stream, c->num_manifolds, c->m[c->cur], c->b, c->sleep_action);
-    hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since);
+    hipLaunchKernelGGL(k_wake_marked, dim3(blocks(c->b.n, 256)), dim3(256), 0, c->stream, c->b.n, c->b, c->sleep_action, c->sleep_since, false);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return set_error(c, EDYNHIP_ERR_HIP, "edynhip_remove_bodies", e);
+    EH_TRY(rename_islands_of_removed_roots(c, gone));
     for (uint32_t k = 0; k < n; ++k) { c->host_kind[indices[k]] = EDYNHIP_KIND_STATIC; c->host_shape[indices[k]] = EDYNHIP_SHAPE_NONE; c->host_removed[indices[k]] = 1; }
     std::vector<uint32_t> &excl = c->exclusions.host;
     if (!excl.empty())
@@ -480,6 +513,7 @@ int edynhip_set_joints(edynhip_ctx *c, uint32_t n, const edynhip_joints *in) {
     EH_HIP(c, hipSetDevice(c->device));
     c->host_joints.clear();
     c->pending_redefs.clear();
+    c->sleep_prev_joints = 0;   // the caller indices start again: none of the new joints is an edge of last step's islands
     if (n) EH_TRY(append_host_joints(c, n, in, "edynhip_set_joints"));
     EH_TRY(rebuild_joints(c, false));
     return reset_new_angles(c, 0);
@@ -494,7 +528,11 @@ int edynhip_add_joints(edynhip_ctx *c, uint32_t n, const edynhip_joints *in, uin
     EH_TRY(append_host_joints(c, n, in, "edynhip_add_joints"));
     int rc = rebuild_joints(c, true);
     if (rc != EDYNHIP_OK) { c->host_joints.resize(first); (void)rebuild_joints(c, false); return rc; }
-    return reset_new_angles(c, first);
+    EH_TRY(reset_new_angles(c, first));
+    // a new edge wakes the islands it joins (insert_to_island, island_manager.cpp:282-294)
+    std::vector<uint32_t> ends;
+    for (size_t k = first; k < c->host_joints.size(); ++k) { ends.push_back(c->host_joints[k].body[0]); ends.push_back(c->host_joints[k].body[1]); }
+    return wake_islands_of(c, ends);
 }
 int edynhip_remove_joints(edynhip_ctx *c, uint32_t n, const uint32_t *indices) {
     if (!c || (n && !indices)) return EDYNHIP_ERR_INVALID;
@@ -634,6 +672,7 @@ int edynhip_set_sleep_timers(edynhip_ctx *c, const uint32_t *island_label, const
     EH_HIP(c, hipStreamSynchronize(c->stream));
     c->sim_clock = clock;
     c->sleep_prev_n = n;
+    c->sleep_prev_joints = (uint32_t)c->host_joints.size();   // the joints came with the state: edges of the islands the timers belong to
     invalidate_graph_changed(c, false);
     c->island_labels_valid = true;
     return EDYNHIP_OK;

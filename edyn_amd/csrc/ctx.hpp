@@ -506,6 +506,7 @@ struct edynhip_ctx {
     // the timer that survives an island merge (islands.hip k_sleep_sizes / k_sleep_carry): last step's labels and body count, sizes of last
     // step's islands, the biggest candidate per new label (size << 32 | ~old label), the carried stamps
     uint32_t *sleep_old_label = nullptr, *sleep_size = nullptr, sleep_prev_n = 0;
+    uint32_t sleep_prev_joints = 0;   // caller joint indices below this existed at the last island update: edges of last step's islands (k_sleep_sizes)
     unsigned long long *sleep_best = nullptr;
     double *sleep_carried = nullptr;
     long df_solves = 0, dfp_solves = 0;   // dataflow velocity / position solves so far while a trace is asked for (EDYNHIP_DF_TRACE_STEP picks one; solver.hip DfTrace)

@@ -173,11 +173,11 @@ __global__ void k_cc_flatten(uint32_t n, const uint32_t *__restrict__ flags, uin
 // merge_islands (island_manager.cpp:297-350): the BIGGEST of the islands that merge - nodes + edges - survives with its sleep timer.
 // Labels are lowest body indices, so the surviving timer is carried to the merged island's label: per new island, the timer of the biggest
 // of last step's islands it consists of; size = its procedural bodies + the edges it had before this step (manifolds that persist from
-// the previous array, joints), ties: the lowest old label (the checker's coloured order counts the same; pinned to the engine by
+// the previous array, joints that existed at the last update), ties: the lowest old label (the checker's coloured order counts the same; pinned to the engine by
 // tests/test_reference_engine.py::test_island_merge_keeps_the_bigger_islands_sleep_timer_like_the_real_engine). Three small passes
 // in the steps of a world with island sleeping that relabel: k_sleep_sizes (sizes of last step's islands, keyed by last step's labels -
 // a copy taken before the hooks, the union-find halves paths in place), the candidate maximum in k_sleep_scan, k_sleep_carry.
-struct SleepMerge { const uint32_t *old_label; uint32_t prev_n; uint32_t *size; unsigned long long *best; double *carried; };
+struct SleepMerge { const uint32_t *old_label; uint32_t prev_n; uint32_t prev_joints; uint32_t *size; unsigned long long *best; double *carried; };
 DI void add_by_label(uint32_t label, uint32_t amount, uint32_t *dst) {   // every lane of the wave calls this (amount 0 = nothing): one atomic per distinct label and wave
     uint64_t todo = __ballot(amount != 0);
     while (todo) {
@@ -218,6 +218,7 @@ __global__ void k_sleep_sizes(uint32_t n, Bodies b, Manifolds mf, uint32_t M, Jo
     add_by_label(label, amount, sm.size);
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < j.n; e += gridDim.x * blockDim.x) {   // joints (few): plain atomics
         const uint32_t a = j.bodyA[e], bb = j.bodyB[e], x = is_dynamic(b.flags[a]) ? a : bb;
+        if (j.orig[e] >= sm.prev_joints) continue;   // made since the last update: a new edge, in no island yet (merge_islands sizes the islands before it inserts them)
         if (x < sm.prev_n && is_dynamic(b.flags[x]) && sm.old_label[x] < n) atomicAdd(&sm.size[sm.old_label[x]], 1u);
     }
 }
@@ -341,12 +342,13 @@ int islands(edynhip_ctx *c) {
     }
     if (sleeping) {
         const bool relabelled = mode != CC_SKIP && c->sleep_old_label != nullptr;
-        SleepMerge sm{c->sleep_old_label, c->sleep_prev_n, c->sleep_size, c->sleep_best, c->sleep_carried};
+        SleepMerge sm{c->sleep_old_label, c->sleep_prev_n, c->sleep_prev_joints, c->sleep_size, c->sleep_best, c->sleep_carried};
         if (!relabelled) sm.best = nullptr;
         if (relabelled) hipLaunchKernelGGL(k_sleep_sizes, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, mf, M, c->j, sm);
         hipLaunchKernelGGL(k_sleep_scan, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, c->sleep_state, sm);
         if (relabelled) hipLaunchKernelGGL(k_sleep_carry, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, sm, c->sleep_since);
         c->sleep_prev_n = n;
+        c->sleep_prev_joints = (uint32_t)c->host_joints.size();
         hipLaunchKernelGGL(k_sleep_edges, dim3(32), dim3(256), 0, s, c->new_edges, c->cnt, c->b.island, c->sleep_state);
         hipLaunchKernelGGL(k_sleep_decide, dim3(blocks(n, 256)), dim3(256), 0, s, n, c->b, c->sleep_state, c->sleep_action, c->sleep_since, c->sim_clock,
                            relabelled ? c->sleep_carried : (const double *)nullptr);

@@ -727,6 +727,16 @@ class World:
         self._check(self._L.edynhip_debug_paths(self._h, C.byref(mask)))
         return {name for name, bit in _capi.PATH_BITS.items() if mask.value & bit}
 
+    def debug_relabel_steps(self):
+        """(full, incremental): how many steps since the context was created relabelled the islands in full (edits and forced relabels
+        included) and how many hooked only the new manifolds onto last step's labels (edynhip_debug_relabel_steps). A step that moved
+        neither was skipped or had nothing to relabel. A world without a context has run none."""
+        if self._h is None:
+            return 0, 0
+        full, inc = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.edynhip_debug_relabel_steps(self._h, C.byref(full), C.byref(inc)))
+        return int(full.value), int(inc.value)
+
     def set_joint_warm_start(self, impulses24, angles=None):
         """Applied impulses ([nj, 24], the layout of get_joint_impulses24) and tracked angles of the joints, by caller index: what a
         world carries into another (edynhip_set_joint_warm_start)."""

@@ -216,14 +216,21 @@ int edynhip_add_bodies(edynhip_ctx *ctx, uint32_t n, const edynhip_bodies *bodie
 /* Joints on a running world: make_constraint / registry.destroy(constraint entity) (include/edyn/util/constraint_util.hpp:38-54,
  * island_manager.cpp:68-97). Joint indices are the order of creation and stay valid for the life of the world (a removed joint
  * keeps its index); applied impulses and hinge angles of the other joints are carried over. *first_index = index of the first
- * joint added. edynhip_set_joint_params = registry.patch<hinge|point_constraint> followed by reset_angle. */
+ * joint added. edynhip_set_joint_params = registry.patch<hinge|point_constraint> followed by reset_angle.
+ * Island sleeping: a new joint wakes the islands of its two bodies (insert_to_island, island_manager.cpp:282-294), a removed joint
+ * the islands it touched (on_destroy_island_resident, :74-97). Such a wake takes the sleeping tags off and nothing else
+ * (wake_up_island, util/island_util.cpp:61-66): the sleep timer of an island that was awake goes on running, and only an island that
+ * the removal really splits starts its timers again. In the step's merge rule a joint counts towards an island's size from the step
+ * after the one that first saw it (merge_islands sizes the islands before it inserts the new edges). */
 int edynhip_add_joints(edynhip_ctx *ctx, uint32_t n, const edynhip_joints *joints, uint32_t *first_index);
 int edynhip_remove_joints(edynhip_ctx *ctx, uint32_t n, const uint32_t *joint_indices);
 int edynhip_set_joint_params(edynhip_ctx *ctx, uint32_t joint_index, const float *params10);
 /* registry.destroy(rigid body) on a running world (src/edyn/edyn.cpp:148-197 hooks, island_manager.cpp:47-115): the body's
  * manifolds and contact points disappear with the next step, joints attached to it are removed, the islands it touched wake
  * up. The body INDEX stays reserved (the slot reads back as a shapeless static body); every other index, manifold, warm-start
- * impulse and sleep timer is untouched. */
+ * impulse and sleep timer is untouched. The wake only takes the sleeping tags off: what is left of the body's own island keeps the
+ * island's sleep timer if it is still in one piece - also when the removed body had the island's lowest index, i.e. was its label:
+ * label and timer move to the lowest body left - and starts again if the removal split it. */
 int edynhip_remove_bodies(edynhip_ctx *ctx, uint32_t n, const uint32_t *body_indices);
 /* Bodies of a running world edited in place: set_rigidbody_mass / _inertia / _friction, rigidbody_set_shape, rigidbody_set_kind
  * (src/edyn/util/rigidbody.cpp:300-362, :471-495, :579-606) without a fresh upload. values holds n entries parallel to indices; only the
@@ -598,12 +605,18 @@ int edynhip_debug_collide(edynhip_ctx *ctx, uint32_t n, const int32_t *shape_typ
 #define EDYNHIP_PATH_LISTS_MOVED        (1ull << 34)  /* a full step rebuilt the candidate lists on the device's own flag (a body left its slack) */
 #define EDYNHIP_PATH_PAIR_SURPLUS       (1ull << 35)  /* some owner reported pairs through the unsorted surplus (more than 64 partners, or a sleeping owner): the surplus sort ran */
 int edynhip_debug_paths(edynhip_ctx *ctx, uint64_t *mask);
+/* Test hook beside edynhip_debug_paths (additive to ABI 15): how many steps since creation brought the island labels up to date with
+ * a full relabel (scene edits and forced relabels included) and how many by hooking only the step's new manifolds onto last step's
+ * labels. A step in which neither number moved was skipped (an unchanged pair set) or had nothing to relabel. Host counters: no kernel
+ * touches them. */
+int edynhip_debug_relabel_steps(edynhip_ctx *ctx, uint64_t *full, uint64_t *incremental);
 
 /* Island sleeping (EDYNHIP_FLAG_SLEEPING): asleep[n] = 1 where the body carries sleeping_tag; wake_all = wake_up_entity on
  * everything (also implied by edynhip_set_state). island_manager.cpp:541-565, util/island_util.cpp:61-66. */
 int edynhip_get_asleep(edynhip_ctx *ctx, uint8_t *asleep);
 int edynhip_wake_all(edynhip_ctx *ctx);
-/* wake_up_entity (util/rigidbody.cpp:409-415 -> island_manager.cpp wake_up_island): wakes the islands of the listed bodies. */
+/* wake_up_entity (util/rigidbody.cpp:409-415 -> wake_up_island, util/island_util.cpp:61-66): wakes the islands of the listed bodies.
+ * The sleeping tags come off; the sleep timer of an island that was awake already is not restarted. */
 int edynhip_wake_bodies(edynhip_ctx *ctx, uint32_t n, const uint32_t *indices);
 /* edyn::set_center_of_mass on a running world (util/rigidbody.cpp:364-370, apply_center_of_mass :517-548): the body's position and linear
  * velocity move to the new centre of mass (given in the shape's frame; zero removes the offset), its origin - shape, contact and joint

@@ -393,6 +393,21 @@ class World:
     def wake_all(self):
         self.L.orc_wake_all(self.h)
 
+    def wake_bodies(self, indices):
+        """wake_up_entity for the listed bodies: their islands wake and the islands' timers start again."""
+        f = self.L.orc_wake_body; f.argtypes = [C.c_void_p, C.c_uint32]; f.restype = None
+        for i in indices:
+            f(self.h, int(i))
+
+    def get_sleep_timers(self):
+        """(island label per body, sleep time stamp by label - negative: no timer running -, clock of the last step): the layout of
+        edyn_amd.World.get_sleep_timers."""
+        n = self.num_bodies
+        lab = np.zeros(n, np.uint32); since = np.zeros(n, np.float64); clock = C.c_double(0)
+        f = self.L.orc_get_sleep_timers; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]; f.restype = None
+        f(self.h, lab.ctypes.data, since.ctypes.data, C.byref(clock))
+        return lab, since, clock.value
+
     def set_joint_warm_start(self, impulses24, angles=None):
         imp = np.ascontiguousarray(impulses24, np.float32)
         ang = None if angles is None else np.ascontiguousarray(angles, np.float32)

@@ -127,6 +127,18 @@ void orc_get_asleep(void *h, uint8_t *out) {
     World *w = (World *)h;
     for (size_t i = 0; i < w->bodies.size(); ++i) out[i] = w->bodies[i].asleep ? 1 : 0;
 }
+// The counterpart of edynhip_get_sleep_timers: every body's island label, the sleep time stamps by label (< 0: no timer running) and the
+// stamp of the last step whose island update has run.
+void orc_get_sleep_timers(void *h, uint32_t *island_label, double *since, double *clock) {
+    World *w = (World *)h;
+    for (size_t i = 0; i < w->bodies.size(); ++i) {
+        island_label[i] = i < w->island_label.size() ? w->island_label[i] : (uint32_t)i;
+        since[i] = i < w->sleep_since.size() ? w->sleep_since[i] : -1.0;
+    }
+    *clock = w->sim_clock;
+}
+// wake_up_entity on a body: its island wakes and the island's timer starts again (island_manager.cpp wake_up_island)
+void orc_wake_body(void *h, uint32_t body) { ((World *)h)->wake_body(body); }
 void orc_step(void *h, int n) { World *w = (World *)h; for (int i = 0; i < n; ++i) w->step(); }
 void orc_run_stage(void *h, int stage) {
     World *w = (World *)h;

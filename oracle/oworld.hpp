@@ -337,6 +337,7 @@ public:
     // island_manager.cpp:605-623): sim_clock is the stamp of the step being run; step() advances it by fixed dt, step_timed()
     // by the caller's stretched step_dt (the max_steps_per_update clamp scales the stamps, not the integration dt).
     double sim_clock = 0;   // the island manager's m_last_time: the stamp of the last step whose island update has run
+    size_t joints_at_update_ = 0;          // joints that existed when the islands were last updated
     std::vector<uint8_t> split_reset_;     // per label: the island is a part of an island that split in this step
     std::vector<double> sleep_since;       // per label: time stamp at which the island first qualified for sleep, < 0 = not counting
     std::vector<uint64_t> new_keys;        // manifolds created by this step's broadphase (they wake their island)
@@ -399,11 +400,23 @@ public:
         if (b.sh.type != SHAPE_NONE) (b.procedural() ? tree_ : np_tree_).destroy(b.leaf);
         b.removed = true; b.kind = KIND_STATIC; b.sh.type = SHAPE_NONE; b.asleep = false;
         b.linvel = b.angvel = {0, 0, 0}; b.mass_inv = 0; b.gravity = {0, 0, 0};
+        // wake_up_island (util/island_util.cpp:61-66) only takes the sleeping tags off: a timer that is running goes on running, and an
+        // island that stays in one piece without the body keeps it (split_islands, island_manager.cpp:421-424)
         for (uint32_t k = 0; k < bodies.size() && k < island_label.size(); ++k)
-            if (bodies[k].procedural() && std::find(wake.begin(), wake.end(), island_label[k]) != wake.end()) {
-                bodies[k].asleep = false;
-                if (island_label[k] < sleep_since.size()) sleep_since[island_label[k]] = -1.0;
+            if (bodies[k].procedural() && std::find(wake.begin(), wake.end(), island_label[k]) != wake.end()) bodies[k].asleep = false;
+        // The island entity outlives its node. Here the island is named by its lowest body index, so when that body goes the name - and
+        // the timer kept under it - moves to the lowest index that is left; the next update then finds last step's island whole or split.
+        if (i < island_label.size() && island_label[i] == i) {
+            uint32_t m = 0xFFFFFFFFu;
+            for (uint32_t k = 0; k < bodies.size() && k < island_label.size(); ++k)
+                if (k != i && bodies[k].procedural() && island_label[k] == i) { m = k; break; }
+            if (m != 0xFFFFFFFFu) {
+                for (uint32_t k = m; k < bodies.size() && k < island_label.size(); ++k)
+                    if (bodies[k].procedural() && island_label[k] == i) island_label[k] = m;
+                if (m < sleep_since.size() && i < sleep_since.size()) sleep_since[m] = sleep_since[i];
             }
+            if (i < sleep_since.size()) sleep_since[i] = -1.0;
+        }
     }
     void remove_joint(uint32_t ji) {
         Joint &j = joints[ji];
@@ -413,9 +426,14 @@ public:
             if (!bodies[e].procedural() || e >= island_label.size()) continue;
             const uint32_t l = island_label[e];
             for (uint32_t k = 0; k < bodies.size() && k < island_label.size(); ++k)
-                if (bodies[k].procedural() && island_label[k] == l) bodies[k].asleep = false;
-            if (l < sleep_since.size()) sleep_since[l] = -1.0;
+                if (bodies[k].procedural() && island_label[k] == l) bodies[k].asleep = false;   // (the timer goes on: wake_up_island only takes the tags off)
         }
+    }
+    void wake_body(uint32_t e) {   // wake_up_entity -> wake_up_island (util/island_util.cpp:61-66): the sleeping tags come off; a running timer goes on
+        if (e >= bodies.size() || !bodies[e].procedural() || e >= island_label.size()) return;
+        const uint32_t l = island_label[e];
+        for (uint32_t k = 0; k < bodies.size() && k < island_label.size(); ++k)
+            if (bodies[k].procedural() && island_label[k] == l) bodies[k].asleep = false;
     }
     void set_gravity(vec3 g) {   // gravity_util.cpp:12-20: the setting and every body that carries a gravity component
         gravity = g;
@@ -454,6 +472,7 @@ public:
         }
         joints.push_back(j);
         joints_coloured_ = false;
+        wake_body(a); wake_body(b);   // a new edge wakes the islands it joins (insert_to_island, island_manager.cpp:282-294)
         return (uint32_t)joints.size() - 1;
     }
 
@@ -786,7 +805,7 @@ public:
         // merge_islands (island_manager.cpp:297-350): when islands merge, the BIGGEST of them - nodes + edges - survives with its
         // sleep_timestamp and takes the others in. Labels here are lowest body indices, so the surviving timer has to be carried to the
         // merged island's label: per new island, the timer of the biggest of last step's islands it is made of, size = procedural bodies
-        // + edges (manifolds that existed before this step, joints); ties: the lowest old label. (The engine's count also has each
+        // + edges (manifolds and joints that existed before this step); ties: the lowest old label. (The engine's count also has each
         // island's non-procedural nodes - a set with history: a static body stays in it after its last edge is gone, until a split
         // rebuilds it - and among equals it keeps the first in an ECS iteration order; both only matter between islands of nearly the same
         // size. Demonstrated against the engine with a four-box scene: tests/test_reference_engine.py::test_island_merge_keeps_the_bigger_*.)
@@ -803,7 +822,11 @@ public:
                 const uint32_t l = old_label(bodies[a].procedural() ? a : b);
                 if (l < n) ++size_old[l];
             }
-            for (auto &j : joints) if (j.alive) { const uint32_t l = old_label(bodies[j.body[0]].procedural() ? j.body[0] : j.body[1]); if (l < n) ++size_old[l]; }
+            // (joints made since the last update are new edges like this step's manifolds: merge_islands sizes the islands before it inserts them)
+            for (size_t k = 0; k < joints.size() && k < joints_at_update_; ++k) {
+                const Joint &j = joints[k];
+                if (j.alive) { const uint32_t l = old_label(bodies[j.body[0]].procedural() ? j.body[0] : j.body[1]); if (l < n) ++size_old[l]; }
+            }
             std::vector<double> carried(n, -1.0);
             std::vector<uint32_t> best(n, 0xFFFFFFFFu);
             for (uint32_t r = 0; r < n && r < prev_label.size(); ++r) {
@@ -822,6 +845,7 @@ public:
             const uint32_t r = prev_label[i];   // last step's root of this body: a body of the same old island
             if (r < n && bodies[r].procedural() && !bodies[r].removed && island_label[r] != island_label[i]) { split_reset_[island_label[i]] = 1; split_reset_[island_label[r]] = 1; }
         }
+        joints_at_update_ = joints.size();
         if (sleeping) update_sleep();   // island_manager::update: put_islands_to_sleep() still sees the PREVIOUS step's stamp ...
         sim_clock = pending_stamp_;     // ... and only then m_last_time = timestamp (island_manager.cpp:533-539)
     }
