@@ -155,7 +155,9 @@ SYMBOLS = ["edynhip_create", "edynhip_destroy", "edynhip_last_error", "edynhip_s
            "edynhip_world_snapshot_records", "edynhip_world_snapshot_map",
            # materials and the mix table on a multi-device world
            "edynhip_world_set_material_extras", "edynhip_world_set_material_ids", "edynhip_world_insert_material_mixing",
-           "edynhip_world_get_point_extras"]
+           "edynhip_world_get_point_extras",
+           # bodies of a running multi-device world edited and woken in place
+           "edynhip_world_edit_bodies", "edynhip_world_wake_bodies"]
 
 _lib = None
 
@@ -291,6 +293,8 @@ def lib():
         L.edynhip_world_set_material_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.edynhip_world_insert_material_mixing.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.edynhip_world_get_point_extras.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.edynhip_world_edit_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Bodies), C.c_uint32]
+        L.edynhip_world_wake_bodies.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_partition_islands.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.edynhip_island_boxes_overlap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.edynhip_get_island_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]

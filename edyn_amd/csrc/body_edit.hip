@@ -188,15 +188,9 @@ __global__ void k_drop_segments(const uint32_t *__restrict__ total, Manifolds ds
     if (nh != hi) dst.seg_end[hi] = m + 1;
 }
 
-}  // namespace eh
-
-using namespace eh;
-
-extern "C" {
-
-int edynhip_edit_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices, const edynhip_bodies *in, uint32_t fields) {
-    if (!c) return EDYNHIP_ERR_INVALID;
-    if (c->world_shard) return set_error(c, EDYNHIP_ERR_UNSUPPORTED, "edynhip_edit_bodies: a shard of a multi-device world takes its bodies from the world");
+// The edit itself: what edynhip_edit_bodies does on its context, and what a multi-device world does on the shard(s) that hold the bodies
+// (multi_body_edit.hip, local indices).
+int edit_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices, const edynhip_bodies *in, uint32_t fields) {
     {
         const char *why = "";
         const int rc = validate_body_edit(n, indices, in, fields, c->b.n, c->host_removed, (uint32_t)c->host_meshes.desc.size(), &why);
@@ -311,6 +305,18 @@ int edynhip_edit_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices, con
     if (kind_changed && joints_touched) EH_TRY(rebuild_joints(c, true));   // the joints' colouring reads who is dynamic
     invalidate_bodies_edited(c, reshape, rekind, dropped);
     return EDYNHIP_OK;
+}
+
+}  // namespace eh
+
+using namespace eh;
+
+extern "C" {
+
+int edynhip_edit_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices, const edynhip_bodies *in, uint32_t fields) {
+    if (!c) return EDYNHIP_ERR_INVALID;
+    if (c->world_shard) return set_error(c, EDYNHIP_ERR_UNSUPPORTED, "edynhip_edit_bodies: a shard of a multi-device world takes its bodies from the world");
+    return edit_bodies(c, n, indices, in, fields);
 }
 
 }  // extern "C"

@@ -622,6 +622,7 @@ EH_LOCAL int rebuild_joints(edynhip_ctx *c, bool fetch);
 EH_LOCAL void mark_islands_of(edynhip_ctx *c, uint32_t n, const uint32_t *list_dev);
 EH_LOCAL void wake_marked_islands(edynhip_ctx *c);
 EH_LOCAL int mesh_bind_body(edynhip_ctx *c, uint32_t body, uint32_t mesh_id);   // mesh.hip: mesh_bind_bodies for one body of a running world
+EH_LOCAL int edit_bodies(edynhip_ctx *c, uint32_t n, const uint32_t *indices, const edynhip_bodies *values, uint32_t fields);   // body_edit.hip: edynhip_edit_bodies without its refusal of a shard
 EH_LOCAL int enqueue_event_prefetch(edynhip_ctx *c);   // capi_readback.hip: this call's event count and list -> the pinned prefetch buffer
 // sort helpers (sort.hip)
 size_t sort_temp_bytes(uint32_t max_items);
@@ -648,6 +649,7 @@ int shard_query_fill(edynhip_ctx *c, int category, uint32_t n, const void *boxes
 // (edynhip_get_point_ids' table, on the device), and the same table written back over the ids edynhip_set_manifolds issued
 constexpr uint32_t kEventTagShift = 28, kEventTagShards = 16;   // id low word: shard << 28 | manifold index << 2 | slot
 int shard_translate_events(edynhip_ctx *c, uint32_t expected, const uint32_t *local_ids_dev, uint32_t n_local, void *out);
+int shard_translate_event_tail(edynhip_ctx *c, uint32_t first, uint32_t last, const uint32_t *local_ids_dev, uint32_t n_local, void *out);   // records [first, last) only, into out[0 ..)
 int shard_gather_point_ids(edynhip_ctx *c, uint64_t *ids_dev);
 int shard_inject_point_ids(edynhip_ctx *c, const uint64_t *ids_dev, uint32_t num_manifolds);
 // world_extras.hip: the current manifold array's point extras (Manifolds::xmat / ximp) as rows[num_manifolds][4][2] float4 on the device

@@ -24,7 +24,7 @@
 // are plain C++ in world_rules.hpp. What touches a device is split by concern, with what the files share in multi.hpp: this file holds the
 // world's life cycle, the scene description, the first build, the step and the plain getters; multi_shard.hip one shard's context and
 // its traffic; multi_partition.hip the monitor kernels, the approach check and the re-partition; multi_edit.hip the edits of a running
-// world; multi_materials.hip materials and the mix table; multi_records.hip the record hand-over; multi_query.hip the queries.
+// world; multi_body_edit.hip the edits of its bodies; multi_materials.hip materials and the mix table; multi_records.hip the record hand-over; multi_query.hip the queries.
 #include "multi.hpp"
 
 using namespace eh;
@@ -36,13 +36,24 @@ namespace {
 // on its shard's stream (behind the translation; the next step of that shard queues up behind the copy). The offsets follow from the
 // counts the shards fetched with their state.
 int append_events(edynhip_world *w) {
-    size_t total = 0;
     for (Shard &s : w->shards) {
         if (s.local_ids.empty() || !s.ctx || !s.res.ev_cnt_host) { s.res.ev_held = 0; continue; }
         if (*s.res.ev_cnt_host > s.ctx->event_cap) w->ev_overflow = true;
         w->ev_occurred += *s.res.ev_cnt_host;
-        total += s.res.ev_held;
     }
+    return append_event_blocks(w);
+}
+
+}  // namespace
+
+namespace eh {
+namespace world {
+
+// The blocks the shards hold translated (Shard res.ev_held records each, in res.ev_out) go to the end of the world's list: after a step
+// (above) and after an edit that destroyed points (multi_body_edit.hip).
+int append_event_blocks(edynhip_world *w) {
+    size_t total = 0;
+    for (const Shard &s : w->shards) total += s.res.ev_held;
     if (total == 0) return EDYNHIP_OK;
     const int home = w->devices[0];
     const size_t need = ((size_t)w->ev_n + total) * sizeof(ContactEvent);
@@ -72,11 +83,6 @@ int append_events(edynhip_world *w) {
     w->ev_n = (uint32_t)at;
     return EDYNHIP_OK;
 }
-
-}  // namespace
-
-namespace eh {
-namespace world {
 
 // the scene's meshes as the island estimate reads them
 MeshRadii scene_meshes(const HostScene &sc) {

@@ -1,4 +1,4 @@
-// What the files of the multi-device world (multi.hip, multi_shard.hip, multi_partition.hip, multi_edit.hip, multi_materials.hip,
+// What the files of the multi-device world (multi.hip, multi_shard.hip, multi_partition.hip, multi_edit.hip, multi_body_edit.hip, multi_materials.hip,
 // multi_records.hip, multi_query.hip) share: the world and its shards, what travels through a re-partition, the error macros, and the functions that cross a
 // file boundary. Internal: nothing here is part of the C-ABI.
 #pragma once
@@ -342,6 +342,9 @@ EH_LOCAL void scene_append_bodies(edynhip_world *w, uint32_t k, const edynhip_bo
 EH_LOCAL void scene_append_joints(HostScene &sc, uint32_t n, const edynhip_joints *in);
 EH_LOCAL HostScene::Def make_def(uint32_t joint, const float *frame_a9, const float *frame_b9, const float *params, bool generic);
 EH_LOCAL void finish_tombstones(edynhip_world *w);
+EH_LOCAL int append_event_blocks(edynhip_world *w);
+// multi_edit.hip: the safety condition after an edit that can bring islands of different shards together
+EH_LOCAL int edit_approach(edynhip_world *w, bool &moved);
 // multi_shard.hip: one shard - its context, what goes up to it and what comes back
 EH_LOCAL int shard_filter_thunk(void *user, uint32_t body, uint32_t other);
 EH_LOCAL void free_shard(Shard &s);

@@ -65,10 +65,12 @@ int make_room(edynhip_world *w, bool joints, std::vector<uint32_t> &extra, const
     return EDYNHIP_OK;
 }
 
+}  // namespace
+
 // The safety condition after an edit that can bring islands of different shards together (a shaped dynamic body was added): the approach
 // check - body boxes while a shard has not stepped since it was built, island boxes otherwise; a new body is an island of its own either
 // way - which also records the boxes the growth monitor measures the new bodies against, and the sticky re-partition if it says "close".
-int edit_approach(edynhip_world *w, bool &moved) {
+int eh::world::edit_approach(edynhip_world *w, bool &moved) {
     moved = false;
     if (w->shards.size() < 2) return EDYNHIP_OK;
     bool per_body = false;
@@ -81,8 +83,6 @@ int edit_approach(edynhip_world *w, bool &moved) {
     ++w->edit_stats.repartitions_by_edit;
     return repartition(w, true, nullptr, nullptr, true);
 }
-
-}  // namespace
 
 extern "C" {
 

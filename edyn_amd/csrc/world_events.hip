@@ -26,6 +26,21 @@ __global__ void __launch_bounds__(256) k_world_translate_events(const ContactEve
     }
 }
 
+// The tail [first, last) of the list, what an edit appended behind the last step's events (edynhip_world_edit_bodies): the host has read
+// both counts, out[i - first] takes record i. One event per lane as above.
+__global__ void __launch_bounds__(256) k_world_translate_event_tail(const ContactEvent *__restrict__ in, uint32_t first, uint32_t last,
+                                                                    const uint32_t *__restrict__ local_ids, uint32_t n_local, ContactEvent *__restrict__ out) {
+    const uint32_t i = first + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= last) return;
+    const uint4 head = *(const uint4 *)__builtin_assume_aligned(&in[i], 8);   // type, step, bodyA, bodyB
+    ContactEvent e;
+    e.type = head.x; e.step = head.y;
+    e.bodyA = head.z < n_local ? local_ids[head.z] : head.z;
+    e.bodyB = head.w < n_local ? local_ids[head.w] : head.w;
+    e.pid = in[i].pid;
+    out[i - first] = e;
+}
+
 // ids[4 m + k] = id of point k of manifold m, 0 where there is no point
 __global__ void __launch_bounds__(256) k_world_gather_pids(uint32_t M, const uint64_t *__restrict__ pid, uint32_t cap, const uint32_t *__restrict__ info,
                                                            uint64_t *__restrict__ ids) {
@@ -58,6 +73,16 @@ int shard_translate_events(edynhip_ctx *c, uint32_t expected, const uint32_t *lo
     if (n == 0) return EDYNHIP_OK;
     hipLaunchKernelGGL(k_world_translate_events, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const ContactEvent *)c->events, (const uint32_t *)c->event_count,
                        c->event_cap, local_ids_dev, n_local, (ContactEvent *)out);
+    EH_HIP(c, hipGetLastError());
+    return EDYNHIP_OK;
+}
+
+int shard_translate_event_tail(edynhip_ctx *c, uint32_t first, uint32_t last, const uint32_t *local_ids_dev, uint32_t n_local, void *out) {
+    if (!c->events) return set_error(c, EDYNHIP_ERR_UNSUPPORTED, "shard_translate_event_tail: the context records no events");
+    last = std::min(last, c->event_cap);   // (out holds event_cap records: last - first of them are written)
+    if (first >= last) return EDYNHIP_OK;
+    hipLaunchKernelGGL(k_world_translate_event_tail, dim3((last - first + 255) / 256), dim3(256), 0, c->stream, (const ContactEvent *)c->events, first, last,
+                       local_ids_dev, n_local, (ContactEvent *)out);
     EH_HIP(c, hipGetLastError());
     return EDYNHIP_OK;
 }

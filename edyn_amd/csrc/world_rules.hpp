@@ -425,4 +425,48 @@ static inline void shards_of_body_range(const int32_t *rank_of, uint32_t first, 
 // point may have been created with a mix that today's materials would not give it again. A world without either carries nothing.
 static inline bool extras_carry_needed(bool any_extras_material_ever, size_t mix_entries) { return any_extras_material_ever || mix_entries != 0; }
 
+// ------------------------------------------------------------------------------------------------ body edits
+// edynhip_world_edit_bodies (multi_body_edit.hip). Shard r takes the edit of a body that is dynamic BEFORE the edit when it owns it, of a
+// replicated one always: an edit goes to every context that holds the body.
+static inline bool shard_takes_body_edit(int32_t kind_before, int32_t rank, uint32_t r) { return shard_holds_body(owner_rank(kind_before, rank), r); }
+// An edit crosses the replication boundary when its kind changes between dynamic and not dynamic: the body changes who holds it.
+static inline bool edit_crosses_boundary(int32_t kind_before, int32_t kind_after) {
+    return (kind_before == EDYNHIP_KIND_DYNAMIC) != (kind_after == EDYNHIP_KIND_DYNAMIC);
+}
+// The kind a body has after an edit of the groups `fields` that names `kind_given` for it
+static inline int32_t kind_after_edit(uint32_t fields, int32_t kind_before, int32_t kind_given) { return (fields & EDYNHIP_EDIT_KIND) ? kind_given : kind_before; }
+// The shard a body made dynamic goes to: the one with the fewest live dynamic bodies (load[W], updated), ties to the lowest shard -
+// place_new_bodies' rule for a body that touches no other of its call.
+static inline uint32_t owner_of_new_dynamic(std::vector<uint32_t> &load) {
+    uint32_t r = 0;
+    for (uint32_t q = 1; q < (uint32_t)load.size(); ++q) if (load[q] < load[r]) r = q;
+    ++load[r];
+    return r;
+}
+// A context keeps the inertia it derived from the shape a body HAD when only the shape is edited; a shard rebuilt from the scene would
+// derive it from the new one. So before a SHAPE edit without INERTIA lands in the scene, the inertia the scene still leaves to the old
+// shape is written out (dbodyinit.hpp shape_inertia, the same float operations in the same order: the inverse the context takes of it is
+// the same bits). Boxes and spheres without a centre-of-mass offset; false: another shape - the scene keeps deriving (DESIGN, not covered).
+static inline bool bake_shape_inertia(int32_t shape_type, const float *p, float mass, bool has_com, float *inertia9) {
+    if (has_com) return false;
+    float d[3];
+    if (shape_type == EDYNHIP_SHAPE_BOX) {
+        const float ex = p[0] * 2.0f, ey = p[1] * 2.0f, ez = p[2] * 2.0f, c = 1.0f / 12.0f * mass;
+        d[0] = c * (ey * ey + ez * ez); d[1] = c * (ez * ez + ex * ex); d[2] = c * (ex * ex + ey * ey);
+    } else if (shape_type == EDYNHIP_SHAPE_SPHERE) {
+        const float s = 0.4f * mass * p[0] * p[0];
+        d[0] = d[1] = d[2] = s;
+    } else return false;
+    for (int k = 0; k < 9; ++k) inertia9[k] = 0.0f;
+    inertia9[0] = d[0]; inertia9[4] = d[1]; inertia9[8] = d[2];
+    return true;
+}
+// An edit makes the approach check due at once when it can bring islands of two shards within the creation margin before the next step: a
+// new shape on a body that is dynamic afterwards, or a body made dynamic. A replicated body is on every shard already; a world of one
+// shard has nobody to approach.
+static inline bool edit_needs_approach_check(uint32_t fields, int32_t kind_before, int32_t kind_after, uint32_t W) {
+    if (W < 2 || kind_after != EDYNHIP_KIND_DYNAMIC) return false;
+    return (fields & EDYNHIP_EDIT_SHAPE) != 0 || kind_before != EDYNHIP_KIND_DYNAMIC;
+}
+
 }  // namespace eh

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 from . import _capi
 from ._capi import EdynHipError, MANIFOLD_DTYPE
-from .world import World, init_config, _ptr
+from .world import World, init_config, _ptr, _edit_arrays
 
 
 class MultiWorld:
@@ -63,6 +63,7 @@ class MultiWorld:
         n, keep, b = World._body_arrays(None, scene)
         self._check(self._L.edynhip_world_set_bodies(self._h, n, C.byref(b)))
         self.n = n
+        self._mat = [keep["friction"].copy(), keep["restitution"].copy()]   # host copy of the materials (edit_bodies: the coefficient not given)
         joints = scene.get("joints") or []
         self.nj = len(joints)
         if joints:
@@ -85,6 +86,7 @@ class MultiWorld:
         first = C.c_uint32(0)
         self._check(self._L.edynhip_world_add_bodies(self._h, n, C.byref(b), C.byref(first)))
         self.n += n
+        self._mat = [np.concatenate([m, keep[k]]) for m, k in zip(self._mat, ("friction", "restitution"))]
         fb = first.value
         fj = self.nj
         joints = scene.get("joints") or []
@@ -142,6 +144,21 @@ class MultiWorld:
         if (p.size, q.size, v.size, o.size) != (3 * self.n, 4 * self.n, 3 * self.n, 3 * self.n):
             raise ValueError("set_state takes the state of every body of the world")
         self._check(self._L.edynhip_world_set_state(self._h, _ptr(p), _ptr(q), _ptr(v), _ptr(o)))
+
+    def edit_bodies(self, indices, mass=None, inertia=None, friction=None, restitution=None, shape_type=None, shape_param=None,
+                    kind=None, gravity=None):
+        """World.edit_bodies on the whole world, global indices, in place (edynhip_world_edit_bodies): same arguments, same defaulting -
+        of friction and restitution the one not given keeps the value last uploaded. A kind that crosses between dynamic and not
+        dynamic rebuilds the shards that gain or lose the body's replica; get_edit_stats() tells the paths apart."""
+        idx, a, b, fields = _edit_arrays(self._mat, indices, mass, inertia, friction, restitution, shape_type, shape_param, kind, gravity)
+        self._check(self._L.edynhip_world_edit_bodies(self._h, len(idx), _ptr(idx), C.byref(b), fields))
+        if fields & _capi.EDIT_MATERIAL:   # (after the call: a refused edit changes nothing)
+            self._mat[0][idx] = a["friction"]; self._mat[1][idx] = a["restitution"]
+
+    def wake_bodies(self, indices):
+        """World.wake_bodies on the whole world: the islands of these bodies wake (edynhip_world_wake_bodies)."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self._L.edynhip_world_wake_bodies(self._h, len(idx), _ptr(idx)))
 
     def get_params(self):
         p = _capi.Params()

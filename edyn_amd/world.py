@@ -84,6 +84,41 @@ def fixed_step_plan(accumulated, elapsed, fixed_dt, max_steps):
     return num_steps, accumulated, fixed_dt
 
 
+def _edit_arrays(mat, indices, mass, inertia, friction, restitution, shape_type, shape_param, kind, gravity):
+    """The arguments of edit_bodies as edynhip_edit_bodies takes them: (indices, arrays by member, the Bodies struct, the field groups).
+    mat: the host copy of (friction, restitution) the coefficient not given is read from. Shared by World and MultiWorld."""
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    n = len(idx)
+    a, fields = {}, 0
+    if mass is not None:
+        a["mass"] = np.ascontiguousarray(np.broadcast_to(np.asarray(mass, np.float32), (n,)))
+        fields |= _capi.EDIT_MASS
+    if inertia is not None:
+        I = np.ascontiguousarray(np.broadcast_to(np.asarray(inertia, np.float32).reshape(-1, 9), (n, 9)))
+        a["has_inertia"] = np.ascontiguousarray(~np.isnan(I).any(axis=1), np.uint8)
+        a["inertia"] = np.ascontiguousarray(np.nan_to_num(I))
+        fields |= _capi.EDIT_INERTIA
+    if friction is not None or restitution is not None:
+        if idx.size and idx.max() >= len(mat[0]):
+            raise EdynHipError(-1, "edit_bodies: body index out of range")
+        a["friction"] = np.ascontiguousarray(np.broadcast_to(np.asarray(mat[0][idx] if friction is None else friction, np.float32), (n,)))
+        a["restitution"] = np.ascontiguousarray(np.broadcast_to(np.asarray(mat[1][idx] if restitution is None else restitution, np.float32), (n,)))
+        fields |= _capi.EDIT_MATERIAL
+    if shape_type is not None:
+        a["shape_type"] = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_type, np.int32), (n,)))
+        a["shape_param"] = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_param, np.float32).reshape(-1, 4), (n, 4)))
+        fields |= _capi.EDIT_SHAPE
+    if kind is not None:
+        a["kind"] = np.ascontiguousarray(np.broadcast_to(np.asarray(kind, np.int32), (n,)))
+        if gravity is not None:
+            a["gravity"] = np.ascontiguousarray(np.broadcast_to(np.asarray(gravity, np.float32).reshape(-1, 3), (n, 3)))
+        fields |= _capi.EDIT_KIND
+    b = _capi.Bodies()
+    for f, _ in _capi.Bodies._fields_:
+        setattr(b, f, _ptr(a.get(f)))
+    return idx, a, b, fields
+
+
 class World:
     """One attached simulation: the analogue of a registry with edyn attached."""
 
@@ -264,35 +299,8 @@ class World:
         (the one not given keeps the value last uploaded); shape_type with shape_param -> SHAPE; kind (with gravity, else the world's) ->
         KIND, which needs mass and inertia for a body made dynamic."""
         self._flush_defs()
-        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        idx, a, b, fields = _edit_arrays(self._mat, indices, mass, inertia, friction, restitution, shape_type, shape_param, kind, gravity)
         n = len(idx)
-        a, fields = {}, 0
-        if mass is not None:
-            a["mass"] = np.ascontiguousarray(np.broadcast_to(np.asarray(mass, np.float32), (n,)))
-            fields |= _capi.EDIT_MASS
-        if inertia is not None:
-            I = np.ascontiguousarray(np.broadcast_to(np.asarray(inertia, np.float32).reshape(-1, 9), (n, 9)))
-            a["has_inertia"] = np.ascontiguousarray(~np.isnan(I).any(axis=1), np.uint8)
-            a["inertia"] = np.ascontiguousarray(np.nan_to_num(I))
-            fields |= _capi.EDIT_INERTIA
-        if friction is not None or restitution is not None:
-            if idx.size and idx.max() >= len(self._mat[0]):
-                raise EdynHipError(-1, "edit_bodies: body index out of range")
-            a["friction"] = np.ascontiguousarray(np.broadcast_to(np.asarray(self._mat[0][idx] if friction is None else friction, np.float32), (n,)))
-            a["restitution"] = np.ascontiguousarray(np.broadcast_to(np.asarray(self._mat[1][idx] if restitution is None else restitution, np.float32), (n,)))
-            fields |= _capi.EDIT_MATERIAL
-        if shape_type is not None:
-            a["shape_type"] = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_type, np.int32), (n,)))
-            a["shape_param"] = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_param, np.float32).reshape(-1, 4), (n, 4)))
-            fields |= _capi.EDIT_SHAPE
-        if kind is not None:
-            a["kind"] = np.ascontiguousarray(np.broadcast_to(np.asarray(kind, np.int32), (n,)))
-            if gravity is not None:
-                a["gravity"] = np.ascontiguousarray(np.broadcast_to(np.asarray(gravity, np.float32).reshape(-1, 3), (n, 3)))
-            fields |= _capi.EDIT_KIND
-        b = _capi.Bodies()
-        for f, _ in _capi.Bodies._fields_:
-            setattr(b, f, _ptr(a.get(f)))
         self._check(self._L.edynhip_edit_bodies(self._h, n, _ptr(idx), C.byref(b), fields))
         if fields & _capi.EDIT_MATERIAL:   # (after the call: a refused edit changes nothing)
             self._mat[0][idx] = a["friction"]; self._mat[1][idx] = a["restitution"]

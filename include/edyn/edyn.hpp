@@ -257,8 +257,9 @@ struct init_config {   // edyn.hpp:39-60 + settings.hpp:21-57
     // the world as it is to one context (edynhip.h "Edits of a RUNNING multi-device world"): bodies and constraints made after attach,
     // their definitions, exclude_collision, registry.destroy of either, edyn::refresh and settings changes keep every contact's warm
     // start, the joints' impulses and angles, sleep timers and the step count - the registry program computes what it computes on one
-    // device, bit for bit. A shape, kind, mass, inertia or friction edit - applied in place on one device (rebuild_on_body_edit) - and a
-    // convex mesh first seen after the bodies went up still rebuild the world from the registry.
+    // device, bit for bit. A shape, kind, mass, inertia or friction edit and wake_up_entity go to the running world too
+    // (edynhip_world_edit_bodies / _wake_bodies; rebuild_on_body_edit is the A/B switch here as on one device). A convex mesh first seen
+    // after the bodies went up and a body left without a shape still rebuild the world from the registry.
     std::vector<int> devices{};
     unsigned max_bodies{0};      // 0 = sized at the first upload (count + 25 % head-room)
     unsigned max_manifolds{0};
@@ -710,7 +711,7 @@ inline void upload_joint_defs(entt::registry &registry, gpu_stepper &s, uint32_t
 // Everything else is appended to / edited on the running world (append_scene_multi, upload_state_multi, apply_params_multi, sync_removed).
 inline void upload_scene_multi(entt::registry &registry, gpu_stepper &s) {
     const uint32_t total = (uint32_t)s.bodies.size(), nj = (uint32_t)s.constraints.size();
-    if (s.world) { edynhip_world_destroy(s.world); s.world = nullptr; s.contacts_resync = true; }   // a new world issues new point ids: the contact entities are rebuilt
+    if (s.world) { edynhip_world_destroy(s.world); s.world = nullptr; s.contacts_resync = true; ++s.tm.context_rebuilds; }   // a new world issues new point ids: the contact entities are rebuilt
     edynhip_config c{};
     c.max_manifolds = s.cfg.max_manifolds;
     c.fixed_dt = s.cfg.fixed_dt;
@@ -1003,11 +1004,18 @@ inline void upload_scene(entt::registry &registry, gpu_stepper &s) {
 // reported as events behind the last step call's: the contact entities of those pairs go, every other entity stays what it is. A mesh the
 // context cannot take, or a body left without a shape, sends the edits down the old road: a context made again from the registry.
 inline void apply_contact_events(entt::registry &registry, gpu_stepper &s, std::vector<edynhip_contact_event> &ev, int rc);
+inline int fetch_contact_events(gpu_stepper &s, edynhip_contact_event *out, uint32_t capacity, uint32_t *n);
+// the id of a polyhedron's mesh on a running multi-device world: its meshes are created before its bodies, so one it has not seen has none
+inline uint32_t world_mesh_id(gpu_stepper &s, const polyhedron_shape &ph, int *rc) {
+    for (auto &known : s.meshes) if (known.first == ph.mesh) return known.second;
+    *rc = EDYNHIP_ERR_UNSUPPORTED;
+    return ~0u;
+}
 inline void flush_body_edits(entt::registry &registry, gpu_stepper &s) {
     if (s.body_edits.empty()) return;
     std::vector<std::pair<uint32_t, uint32_t>> edits;
     edits.swap(s.body_edits);
-    if (!s.ctx) return;
+    if (!s.ctx && !s.world) return;
     constexpr uint32_t drops = EDYNHIP_EDIT_SHAPE | EDYNHIP_EDIT_KIND;
     std::vector<std::pair<uint32_t, uint32_t>> todo;   // (groups, body), sorted: one call per set of groups
     bool any_drop = false;
@@ -1026,12 +1034,12 @@ inline void flush_body_edits(entt::registry &registry, gpu_stepper &s) {
     auto rebuild_instead = [&]() {
         for (auto &t : todo) { if (t.first & drops) s.reshaped.push_back(t.second); if (t.first & EDYNHIP_EDIT_MATERIAL) s.refresh_friction = true; }
         s.recreate = s.scene_dirty = true;
-        upload_scene(registry, s);
+        if (s.multi()) upload_scene_multi(registry, s); else upload_scene(registry, s);
     };
     uint32_t seen = 0;
     int rc_seen = EDYNHIP_OK;
     const bool mirror = any_drop && s.cfg.materialize_contacts;
-    if (mirror) rc_seen = edynhip_get_contact_events(s.ctx, nullptr, 0, &seen);   // the events already carried into the registry
+    if (mirror) rc_seen = fetch_contact_events(s, nullptr, 0, &seen);   // the events already carried into the registry
     for (size_t at = 0; at < todo.size();) {
         size_t end = at;
         while (end < todo.size() && todo[end].first == todo[at].first) ++end;
@@ -1042,7 +1050,7 @@ inline void flush_body_edits(entt::registry &registry, gpu_stepper &s) {
         int mesh_rc = EDYNHIP_OK;
         fill_body_arrays(registry, s, 0, n, A, [&](const polyhedron_shape &ph) {
             int rc = EDYNHIP_OK;
-            const uint32_t id = (g & EDYNHIP_EDIT_SHAPE) ? context_mesh_id(s, ph, &rc) : 0u;
+            const uint32_t id = (g & EDYNHIP_EDIT_SHAPE) ? (s.world ? world_mesh_id(s, ph, &rc) : context_mesh_id(s, ph, &rc)) : 0u;
             if (rc != EDYNHIP_OK) mesh_rc = rc;
             return id;
         }, list.data());
@@ -1050,14 +1058,14 @@ inline void flush_body_edits(entt::registry &registry, gpu_stepper &s) {
         if (g & EDYNHIP_EDIT_SHAPE) for (uint32_t k = 0; k < n; ++k) shapeless = shapeless || A.stype[k] == EDYNHIP_SHAPE_NONE;
         if (mesh_rc != EDYNHIP_OK || shapeless) { rebuild_instead(); return; }
         const edynhip_bodies b = A.view();
-        check(s, edynhip_edit_bodies(s.ctx, n, list.data(), &b, g));
+        check(s, s.world ? edynhip_world_edit_bodies(s.world, n, list.data(), &b, g) : edynhip_edit_bodies(s.ctx, n, list.data(), &b, g));
         at = end;
     }
     if (mirror) {
         uint32_t n = 0;
-        int rc = edynhip_get_contact_events(s.ctx, nullptr, 0, &n);
+        int rc = fetch_contact_events(s, nullptr, 0, &n);
         std::vector<edynhip_contact_event> ev(n);
-        if (rc == EDYNHIP_OK && n) rc = edynhip_get_contact_events(s.ctx, ev.data(), n, &n);
+        if (rc == EDYNHIP_OK && n) rc = fetch_contact_events(s, ev.data(), n, &n);
         if (rc != EDYNHIP_OK || rc_seen != EDYNHIP_OK || seen > n) { s.contacts_resync = true; return; }   // (a list that overflowed: the entities are rebuilt from the manifolds)
         ev.erase(ev.begin(), ev.begin() + seen);
         phase_timer t(s.tm.contacts);
@@ -1467,6 +1475,7 @@ inline void run_steps_of_update(entt::registry &registry, gpu_stepper &s, unsign
             if (!s.world || s.recreate) upload_scene_multi(registry, s);
             else if (s.scene_dirty) append_scene_multi(registry, s);
             if (!s.material_dirty.empty()) flush_materials(registry, s);
+            if (!s.body_edits.empty()) flush_body_edits(registry, s);
             if (s.state_dirty) upload_state(registry, s);
             apply_params(s);
         }
@@ -2484,18 +2493,19 @@ inline void set_kinematic_orientation(entt::registry &registry, entt::entity ent
 namespace detail {
 // An edit of a body's mass, inertia, material, shape or kind (EDYNHIP_EDIT_* groups). A body the context already holds is edited in
 // place at the next update (flush_body_edits); one that has not gone up yet takes its components with it. The road from before
-// edynhip_edit_bodies - the next upload re-creates the context - is taken with init_config::rebuild_on_body_edit, on a world over
-// several devices, and where the edit has no in-place form (a body left without a shape).
+// edynhip_edit_bodies - the next upload re-creates the context, or the world over several devices - is taken with
+// init_config::rebuild_on_body_edit and where the edit has no in-place form (a body left without a shape). On init_config::devices the
+// edits go through edynhip_world_edit_bodies.
 inline void record_body_edit(entt::registry &registry, entt::entity entity, uint32_t groups, bool in_place_form = true) {
     auto &s = registry.ctx().get<gpu_stepper>();
     const body_index *bi = registry.try_get<body_index>(entity);
-    if (s.cfg.rebuild_on_body_edit || s.multi() || !in_place_form) {
+    if (s.cfg.rebuild_on_body_edit || !in_place_form) {
         s.recreate = s.scene_dirty = true;
         if (groups & EDYNHIP_EDIT_MATERIAL) s.refresh_friction = true;
         if ((groups & (EDYNHIP_EDIT_SHAPE | EDYNHIP_EDIT_KIND)) && bi) s.reshaped.push_back(bi->value);
         return;
     }
-    if (!bi || !s.ctx || bi->value >= s.uploaded_bodies) return;
+    if (!bi || (!s.ctx && !s.world) || bi->value >= s.uploaded_bodies) return;
     for (auto &e : s.body_edits) if (e.first == bi->value) { e.second |= groups; return; }
     s.body_edits.emplace_back(bi->value, groups);
 }
@@ -2540,8 +2550,8 @@ inline void rigidbody_set_kind(entt::registry &registry, entt::entity entity, ri
 /// rigidbody.cpp:409-415 -> island_manager wake_up_island
 inline void wake_up_entity(entt::registry &registry, entt::entity entity) {
     auto &s = registry.ctx().get<detail::gpu_stepper>();
-    if (auto *bi = registry.try_get<detail::body_index>(entity); bi && s.ctx && bi->value < s.uploaded_bodies && !s.scene_dirty)
-        detail::check(s, edynhip_wake_bodies(s.ctx, 1, &bi->value));
+    if (auto *bi = registry.try_get<detail::body_index>(entity); bi && (s.ctx || s.world) && bi->value < s.uploaded_bodies && !s.scene_dirty)
+        detail::check(s, s.world ? edynhip_world_wake_bodies(s.world, 1, &bi->value) : edynhip_wake_bodies(s.ctx, 1, &bi->value));
 }
 
 /// util/island_util.hpp:20-26: in the sequential stepper wake_up_entity IS wake_up_island_resident (rigidbody.cpp:409-415)

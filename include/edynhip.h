@@ -802,7 +802,7 @@ int edynhip_world_get_point_ids(edynhip_world *w, uint64_t *ids, uint32_t capaci
 typedef struct {
     uint32_t edits;                   /* edit calls that changed a built world */
     uint32_t in_place;                /* ... of which ran without rebuilding a shard and without a re-partition */
-    uint32_t shard_rebuilds;          /* shards rebuilt with head-room because an add did not fit */
+    uint32_t shard_rebuilds;          /* shards rebuilt with head-room because an add did not fit, or because a body's kind crossed between dynamic and not */
     uint32_t repartitions_by_edit;    /* sticky re-partitions an edit caused (close islands, a joint between two shards) */
     uint32_t approach_checks_by_edit; /* approach checks run right after an edit */
 } edynhip_world_edit_stats;
@@ -816,6 +816,38 @@ int edynhip_world_set_state(edynhip_world *w, const float *pos, const float *orn
 int edynhip_world_get_params(edynhip_world *w, edynhip_params *out);
 int edynhip_world_set_params(edynhip_world *w, const edynhip_params *params);
 int edynhip_world_get_edit_stats(edynhip_world *w, edynhip_world_edit_stats *out);
+/* edynhip_edit_bodies / edynhip_wake_bodies on a multi-device world (additive to ABI 15): same arguments, field groups
+ * (EDYNHIP_EDIT_MASS .. _KIND) and per-group semantics, GLOBAL body indices. After any sequence of these calls, the other world edits and
+ * steps the world returns, bit for bit, what ONE context holding the whole scene returns - state, manifolds, sleeping tags, the multiset of
+ * contact events, point ids up to the known renaming, queries, records - right after the call and after every later step.
+ *   where     an edit of a dynamic body goes to the shard that owns it, an edit of a replicated (static or kinematic) body to every
+ *             shard, each in that shard's local indices on the shard's own thread; a polyhedron edit first creates the mesh on a shard
+ *             that lacks it. The scene stays the truth: every edited member lands in the world's description, so whatever rebuilds a
+ *             shard later produces the edited body. A body made static has zero velocities in edynhip_world_get_state at once.
+ *   in place  MASS, INERTIA, MATERIAL, SHAPE, KIND between kinematic and static, KIND on a body that stays dynamic: no shard is rebuilt,
+ *             nothing is re-partitioned (unless the safety rule below asks), nothing sized by a shard is read back or uploaded
+ *             (edynhip_world_edit_stats: edits + 1, in_place + 1). With one shard every edit is in place.
+ *   crossing  KIND between dynamic and not dynamic changes who holds the body. Local indices ascend with the global ones, so the body cannot
+ *             be appended to another shard's context. Dynamic to static / kinematic: the owner is edited in place (the drop, the events, the
+ *             wakes), the body becomes replicated, and the OTHER shards are rebuilt, with the replica, through what a sticky re-partition
+ *             carries. Static / kinematic to dynamic: every shard edits its replica in place (each drops its own manifolds of the body, emits
+ *             their events, wakes the partners: the union is what one context does), the body goes to the shard that owns the fewest live
+ *             dynamic bodies (ties: the lowest shard) and the other shards are rebuilt without it; joints of the body to islands of other
+ *             shards move those islands together as edynhip_world_add_joints does. Warm starts, joint impulses and angles, sleep tags and
+ *             timers, point ids and the step count survive. Counted in shard_rebuilds / repartitions_by_edit, not in in_place.
+ *   safety    a SHAPE edit of a dynamic body, or a KIND edit to dynamic, can bring islands of two shards within the creation margin before
+ *             the next step: the world runs the approach check at once (which also refreshes the growth monitor's reference boxes) and the
+ *             sticky re-partition if it says "close". Edits of replicated bodies need no check.
+ *   events    with EDYNHIP_FLAG_CONTACT_EVENTS the POINT_DESTROYED / MANIFOLD_DESTROYED records of a SHAPE or KIND edit are translated on
+ *             the shard's device (the tail of its list only) and appended to the world's list: edynhip_world_get_contact_events then
+ *             returns the last step call's events plus the edit's, as one context does. Without the flag none of this runs.
+ *   described on a world that is described but not built the call alters the description only.
+ *   errors    what edynhip_edit_bodies refuses (index out of range, a removed body, an index listed twice, a bad mesh id, dynamic without
+ *             MASS + INERTIA, an unknown group ...), decided before anything changes on any shard: the world is left as it was.
+ * edynhip_world_wake_bodies: out-of-range indices are refused, removed bodies accepted and ignored; forwarded to the shards that hold the
+ * bodies (a body's island lives on one shard); counts as an in-place edit; does nothing without EDYNHIP_FLAG_SLEEPING or on an unbuilt world. */
+int edynhip_world_edit_bodies(edynhip_world *w, uint32_t n, const uint32_t *indices, const edynhip_bodies *values, uint32_t fields);
+int edynhip_world_wake_bodies(edynhip_world *w, uint32_t n, const uint32_t *indices);
 /* edynhip_set_material_extras / _set_material_ids / _insert_material_mixing / _get_point_extras on a multi-device world (additive to ABI 15):
  * same arguments, same rules, GLOBAL body indices, before the first step or on a running world. The world returns, bit for bit, what ONE
  * context holding the whole scene returns after the same calls and steps.
